@@ -8,6 +8,11 @@ hop (300 samples = 1 frame) per stream per step, streaming state carried across 
 hot path over one batch of synthetic audio already resident in HBM.
 
 Prints ONE JSON line (rank 0).  value = frames/s for the whole job.
+
+A plain run sets up, warms up, times `--steps` steps and prints the line.  Everything else it can measure or check
+(latencies, the per-op profile and rooflines, the other precision, the guard legs, the parity self-check, the extra
+configurations, the CPU baselines) runs only with `--full`.  `--dump-outputs DIR` writes the waveforms the last timed
+step handed back (DIR/audio.npy, float32) for comparing two builds output for output; the inputs are seeded.
 """
 import argparse
 import json
@@ -29,6 +34,7 @@ FP32_MFMA_PEAK_TFLOPS = 157.3      # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32
 F16_MFMA_PEAK_TFLOPS = 2500.0      # MI355X_MICROARCH.md: dense f16/bf16 MFMA peak; a split-f16 product sum issues 3 of them
 HBM_PEAK_GBS = 8000.0              # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 PMC_MARKER_N = 7654321                         # --pmc-markers: element count of the marker launches
+DUMP_LIMIT_BYTES = 64 << 20                    # --dump-outputs: most bytes written by one run, all ranks together
 PMC_TRAFFIC_FILE = "r6_pmc_traffic.csv"        # rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over this bench, pipelined schedule (tools/profile_round.sh)
 STEADY_STATS_FILE = "r6_kernel_stats_steady.csv"   # rocprofv3 --kernel-trace over the timed steps of the same schedule (tools/trace_summary.py)
 SERIAL_STATS_FILE = "r6_kernel_stats_serial.csv"   # ... of `bench.py --serial` (one HIP stream, nothing else on the chip)
@@ -80,6 +86,21 @@ def step(ad, x):
     idx = ad.tx_encoder.quantize(z)
     zq = ad.rx_encoder.lookup(idx)
     return ad.decoder.decode(zq)
+
+
+def dump_outputs(dirname, y, rank, world):
+    """--dump-outputs: what the last timed step returned to its caller -- the waveform batch y (B, 1, samples), one per group of streams --
+    as float32 DIR/audio.npy (rank r > 0: audio_rank<r>.npy).  Beyond this rank's share of DUMP_LIMIT_BYTES a fixed, seeded sample of
+    whole streams is written instead, with their stream ids (rank-local) in audio_streams.npy."""
+    a = torch.cat([t.cpu() for t in (y if isinstance(y, list) else [y])], 0).float().numpy()      # (.cpu() settles a lazily guarded result)
+    tag = "" if rank == 0 else f"_rank{rank}"
+    os.makedirs(dirname, exist_ok=True)
+    keep = max(1, (DUMP_LIMIT_BYTES // world) // (a[0].nbytes + 8))
+    if len(a) > keep:
+        ids = np.sort(np.random.default_rng(SEED).choice(len(a), keep, replace=False))
+        np.save(os.path.join(dirname, f"audio_streams{tag}.npy"), ids.astype(np.float64))
+        a = a[ids]
+    np.save(os.path.join(dirname, f"audio{tag}.npy"), np.ascontiguousarray(a))
 
 
 def TxRxPipeline(ad, dev, depth=4):
@@ -923,8 +944,15 @@ def main():
     ap.add_argument("--no-guarded", action="store_true", help="skip the legs that time the other guard modes (guard off; every program step checked synchronously)")
     ap.add_argument("--guard", choices=("default", "off"), default="default",
                     help="default: AudioDec's default guard (on; deferred in the pipeline of the timed region).  off: AudioDec(guard=False), as rounds 1-4 timed")
-    ap.add_argument("--dump-ops", type=str, default=None, help="write the per-op HIP-event table (CSV) here")
+    ap.add_argument("--dump-ops", type=str, default=None, help="write the per-op HIP-event table (CSV) here; implies --full (the table comes from its per-op profile)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every other leg: latencies, per-op profile and rooflines, the other precision, the "
+                         "guard legs, the parity self-check, the extra configurations and the CPU baselines (each still subject to its --no-* flag)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one returned to its caller as DIR/audio.npy (float32, (streams, 1, samples); "
+                         "rank r > 0: audio_rank<r>.npy); above %d MB a fixed, seeded sample of whole streams plus their ids (audio_streams.npy)" % (DUMP_LIMIT_BYTES >> 20))
     args = ap.parse_args()
+    full = args.full or args.dump_ops is not None
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` launches its own N ranks (one process per GPU over RCCL) and relays their exit code;
@@ -1041,6 +1069,8 @@ def main():
         elapsed = time.perf_counter() - t0
         if args.pmc_markers:
             torch.arange(PMC_MARKER_N, device=dev); torch.cuda.synchronize()
+    if args.dump_outputs:                          # before anything else steps these models
+        dump_outputs(args.dump_outputs, y, rank, world)
     elapsed_rank = elapsed
     elapsed = shard.max_over_ranks(elapsed, coll_dev)
     per_rank = shard.gather_floats(B * args.steps * FPS / elapsed_rank, coll_dev)      # every rank's own frames/s over ITS timed region
@@ -1096,6 +1126,31 @@ def main():
                                 "checkpoint broadcast, the barrier around the timed region and the max / gather of the elapsed times"},
         "realtime_streams_supported_per_gpu": int(frames / elapsed / world / 160.0),
     }
+
+    def report(out):
+        # sticky device-side error flags of the HIP library (0 = clean; see adk_debug_flags in the header)
+        import ctypes
+        from audiodec_amd import native
+        flags = ctypes.c_int32(0)
+        native.check(native.lib().adk_debug_flags(ctypes.byref(flags)), "adk_debug_flags")
+        out["device_error_flags"] = int(flags.value)
+        assert flags.value == 0, f"device error flags {flags.value}: results invalid"
+        if "self_check" in out:
+            assert out["self_check"]["ok"], f"parity check of the timed configuration failed: {out['self_check']}"
+        if "self_check" in out.get("roofline_convtr_T5", {}):
+            assert out["roofline_convtr_T5"]["self_check"]["ok"], f"parity check of the 5-frames-per-call configuration failed: {out['roofline_convtr_T5']['self_check']}"
+        for k_, v_ in out.get("extra_configs", {}).items():
+            if isinstance(v_, dict) and "self_check" in v_:
+                assert v_["self_check"]["ok"], f"parity check of {k_} failed: {v_['self_check']}"
+        if rank == 0:
+            print(json.dumps(finish_line(out)))
+        if world > 1:
+            dist.destroy_process_group()
+
+    if not full:                                   # the plain run: the headline only
+        del out["latency_ms"]
+        report(out)
+        return
 
     # per-batch latency: device-complete time of ONE encode -> RVQ -> lookup -> decode pass, serial, synchronised
     def batch_latency():
@@ -1321,24 +1376,7 @@ def main():
                 out["cpu_baseline"]["config1_file_roundtrip"] = cpu_cfg1()
                 out["cpu_baseline"]["config1_file_roundtrip_more_cores"] = cpu_cfg1(threads=many, reps=2)
             torch.set_num_threads(4)
-    # sticky device-side error flags of the HIP library (0 = clean; see adk_debug_flags in the header)
-    import ctypes
-    from audiodec_amd import native
-    flags = ctypes.c_int32(0)
-    native.check(native.lib().adk_debug_flags(ctypes.byref(flags)), "adk_debug_flags")
-    out["device_error_flags"] = int(flags.value)
-    assert flags.value == 0, f"device error flags {flags.value}: results invalid"
-    if "self_check" in out:
-        assert out["self_check"]["ok"], f"parity check of the timed configuration failed: {out['self_check']}"
-    if "self_check" in out.get("roofline_convtr_T5", {}):
-        assert out["roofline_convtr_T5"]["self_check"]["ok"], f"parity check of the 5-frames-per-call configuration failed: {out['roofline_convtr_T5']['self_check']}"
-    for k_, v_ in out.get("extra_configs", {}).items():
-        if isinstance(v_, dict) and "self_check" in v_:
-            assert v_["self_check"]["ok"], f"parity check of {k_} failed: {v_['self_check']}"
-    if rank == 0:
-        print(json.dumps(finish_line(out)))
-    if world > 1:
-        dist.destroy_process_group()
+    report(out)
 
 
 if __name__ == "__main__":

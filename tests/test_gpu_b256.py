@@ -241,7 +241,7 @@ def test_bench_n_ranks_rehearsal_on_one_gpu(gpu, ranks):
     env = dict(os.environ, ADK_BENCH_BACKEND="gloo", ADK_BENCH_ONE_GPU="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "LOCAL_WORLD_SIZE"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(ranks), "--steps", "6", "--warmup", "2", "--preroll", "8", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(ranks), "--steps", "6", "--warmup", "2", "--preroll", "8", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -266,6 +266,36 @@ def test_bench_n_ranks_rehearsal_on_one_gpu(gpu, ranks):
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1"],
                            capture_output=True, text=True, timeout=300, env=env, cwd=root)
         assert r.returncode != 0 and "HIP device(s) visible" in r.stderr and not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+def test_plain_bench_times_only_the_headline_and_dumps_its_outputs(gpu, tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: exactly K timed steps, the headline keys and none of the
+    legs behind --full; DIR/audio.npy is the waveform batch of the last timed step, and a second run with the same arguments
+    writes the same waveforms (seeded inputs)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "ADK_BENCH_ONE_GPU")}
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--preroll", "4", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        out = json.loads(lines[0])
+        assert out["steps"] == 5 and out["warmup"] == 2 and out["n_gpus"] == 1 and out["device_error_flags"] == 0
+        assert out["unit"] == "frames/s" and out["higher_is_better"] is True and out["dtype"].startswith("f32") and "frames/s" in out["metric"]
+        assert out["value"] > 0 and abs(out["value"] - 256 * 5 / (out["ms_per_step"] * 5e-3)) < 0.01 * out["value"]
+        for k in ("roofline", "cpu_baseline", "self_check", "other_precision", "unguarded", "extra_configs", "latency_ms"):
+            assert k not in out, k
+        assert sorted(os.listdir(d)) == ["audio.npy"]
+        a = np.load(d / "audio.npy")
+        assert a.dtype == np.float32 and a.shape == (256, 1, HOP) and np.isfinite(a).all() and np.abs(a).max() > 0
+        dumps.append(a)
+    assert np.abs(dumps[0] - dumps[1]).max() <= WAVE_TOL
 
 
 @pytest.mark.parametrize("split16", [True, False], ids=["split16", "f32"])

@@ -320,6 +320,26 @@ def test_pmc_summary_keeps_only_the_marked_region(tmp_path):
     assert body[1].startswith('"conv_sk_kernel<2, 2, 1, 2, true, 1>",122880,256,2,1.00,20.00,10.00,30.00,40.0,100.00,'), body[1]
 
 
+def test_bench_dump_outputs_writes_float32_and_samples_whole_streams(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs): the groups' waveform batches concatenated, as float32; beyond the byte budget (shared by the
+    ranks) a seeded sample of whole streams with their ids -- the same sample in every run."""
+    import bench
+    y = torch.arange(6 * 10, dtype=torch.float64).reshape(6, 1, 10)
+    bench.dump_outputs(str(tmp_path / "all"), [y[:3], y[3:]], 0, 1)
+    a = np.load(tmp_path / "all" / "audio.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, y.numpy()) and sorted(os.listdir(tmp_path / "all")) == ["audio.npy"]
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 2 * 2 * (40 + 8))          # two ranks, room for two 10-sample streams each
+    for run in ("s0", "s1"):
+        bench.dump_outputs(str(tmp_path / run), y, 1, 2)
+        assert sorted(os.listdir(tmp_path / run)) == ["audio_rank1.npy", "audio_streams_rank1.npy"]
+        assert sum(os.path.getsize(tmp_path / run / f) - 128 for f in os.listdir(tmp_path / run)) <= bench.DUMP_LIMIT_BYTES // 2   # (128 B: .npy header)
+    ids = np.load(tmp_path / "s0" / "audio_streams_rank1.npy")
+    s = np.load(tmp_path / "s0" / "audio_rank1.npy")
+    assert ids.dtype == np.float64 and len(ids) == 2 and np.all(np.diff(ids) > 0)
+    assert np.array_equal(s, y.numpy()[ids.astype(int)].astype(np.float32))
+    assert np.array_equal(ids, np.load(tmp_path / "s1" / "audio_streams_rank1.npy"))
+
+
 def test_bench_gpus_n_launches_its_own_ranks_or_fails_loudly():
     """`python bench.py --gpus N` without a torchrun environment re-executes itself under torch.distributed.run with N ranks
     (bench.self_launch); with fewer than N HIP devices visible that is an error (rc 2, a message, no JSON line) -- never a silent

@@ -4,7 +4,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
 tag=$1; name=$2; rounds=$3; shift 3
 mkdir -p gpurun_out
-ARGS="--steps 100 --warmup 10 --no-cpu-baseline --no-extra-configs --no-other-precision --no-guarded --no-t5 --no-self-check"
+ARGS="--full --steps 100 --warmup 10 --no-cpu-baseline --no-extra-configs --no-other-precision --no-guarded --no-t5 --no-self-check"
 for r in $(seq 1 $rounds); do
   for v in "$@"; do
     f=$(echo "$v" | tr '/ ,' '___' | tail -c 40)

@@ -6,7 +6,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
 tag=$1; name=$2; va=$3; vb=$4; rounds=${5:-2}
 mkdir -p gpurun_out
-ARGS="--steps 100 --warmup 10 --no-cpu-baseline --no-extra-configs --no-other-precision --no-guarded --no-t5 --no-self-check"
+ARGS="--full --steps 100 --warmup 10 --no-cpu-baseline --no-extra-configs --no-other-precision --no-guarded --no-t5 --no-self-check"
 for r in $(seq 1 $rounds); do
   for v in $va $vb; do
     f=$(echo "$v" | tr '/ ' '__' | tail -c 40)          # (a value may be a path: ADK_LIB_PATH)

@@ -2,8 +2,8 @@
 # One GPU-box session: tools/gpu_session.sh <tag> [what ...]   (run through gpurun; logs under gpurun_out/<tag>_*)
 #   chains   the residual-chain bit-identity tests + the benched-configuration parity test
 #   tests    the whole GPU suite
-#   bench    python bench.py (default run) with the per-op table
-#   quick    python bench.py without CPU legs / extra configs / other precision
+#   bench    python bench.py with every leg and the per-op table (--dump-ops implies --full)
+#   quick    python bench.py, every leg but the CPU legs / extra configs / other precision
 #   kbench   build tools/bin/kbench
 cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp

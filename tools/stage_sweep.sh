@@ -3,7 +3,7 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
 mkdir -p gpurun_out
-ARGS="--steps 100 --warmup 10 --no-cpu-baseline --no-extra-configs --no-other-precision --no-guarded --no-t5 --no-self-check --no-op-profile"
+ARGS="--full --steps 100 --warmup 10 --no-cpu-baseline --no-extra-configs --no-other-precision --no-guarded --no-t5 --no-self-check --no-op-profile"
 for st in "$@"; do
   for r in 1 2; do
     timeout 300 python bench.py $ARGS --stages "$st" > gpurun_out/stages_$(echo $st | tr ',' '_')_$r.json 2> gpurun_out/stages.err
