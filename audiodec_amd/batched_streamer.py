@@ -13,7 +13,10 @@ on the GPU:
   * per-stream reset / join: ``reset_stream(b)`` restores the warmed-up codec state of that stream only;
   * latency / drop accounting per stream with the reference's rule (latency > max_latency: pending
     frames of that stream are discarded and counted);
-  * transport between transmitter and receiver is the 80 bit/frame payload of ``wire.py``.
+  * transport between transmitter and receiver is the 80 bit/frame payload of ``wire.py``;
+  * opt-in code usage (``track_codebook_usage=True``): every tick's latents and codes are folded into a device-side
+    ``codebook_usage.CodebookUsage``; ``stats()`` then reports each stage's perplexity and dead codes -- dead codes, a
+    collapsed stage or a wrong checkpoint do not look like healthy traffic.
 """
 import collections
 import time
@@ -25,7 +28,8 @@ from . import native
 
 
 class BatchedAudioDecStreamer:
-    def __init__(self, audiodec, frame_size, sample_rate=48000, gain=1.0, max_latency=0.1, use_wire_format=True):
+    def __init__(self, audiodec, frame_size, sample_rate=48000, gain=1.0, max_latency=0.1, use_wire_format=True,
+                 track_codebook_usage=False):
         self.tx, self.rx, self.dec = audiodec.tx_encoder, audiodec.rx_encoder, audiodec.decoder
         self.n = self.tx.num_streams
         assert self.dec.num_streams == self.n
@@ -43,6 +47,10 @@ class BatchedAudioDecStreamer:
         self.payload_bytes = 0
         self._x = torch.zeros(self.n, 1, frame_size, dtype=torch.float32, device=self.dev)
         self._host = torch.zeros(self.n, 1, frame_size, dtype=torch.float32).pin_memory() if torch.cuda.is_available() else None
+        self.usage = None
+        if track_codebook_usage:
+            from .codebook_usage import CodebookUsage
+            self.usage = CodebookUsage(self.tx)
 
     # ---- per-stream control ----
     def push(self, stream, frame):
@@ -79,7 +87,8 @@ class BatchedAudioDecStreamer:
         self._x.copy_(self._host, non_blocking=True)
         t0 = time.time()
         with torch.no_grad():
-            idx = self.tx.quantize(self.tx.encode(self._x))
+            z = self.tx.encode(self._x)
+            idx = self.tx.quantize(z)
             if self.use_wire:
                 payload = self.tx.pack(idx, check=False)                    # what would cross the network: 10 bytes / frame / stream
                 self.payload_bytes += payload.numel()
@@ -95,11 +104,13 @@ class BatchedAudioDecStreamer:
         for s in range(self.n):
             if stamps[s] is not None:
                 self.latencies[s].append(t2 - stamps[s])
+        if self.usage is not None:
+            self.usage.update(z, idx)              # verified codes (a guard repair has rewritten them by now); enqueued, not waited for
         return out
 
     def stats(self):
         lat = np.concatenate([np.asarray(l) for l in self.latencies if l]) if any(self.latencies) else np.zeros(1)
-        return {
+        st = {
             "streams": self.n, "ticks": max(self.n_frames) if self.n_frames else 0,
             "encoder_ms_mean": float(np.mean(self.encoder_times) * 1e3) if self.encoder_times else 0.0,
             "decoder_ms_mean": float(np.mean(self.decoder_times) * 1e3) if self.decoder_times else 0.0,
@@ -107,6 +118,10 @@ class BatchedAudioDecStreamer:
             "underruns": int(sum(self.underruns)), "frame_drops": int(sum(self.frame_drops)),
             "payload_kbps_per_stream": (8.0 * self.payload_bytes / max(sum(self.n_frames), 1)) * (self.sample_rate / self.frame_size) / 1e3,
         }
+        if self.usage is not None:
+            st["codebook_perplexity"] = [float(v) for v in self.usage.perplexity()]
+            st["codebook_dead_codes"] = [int(v) for v in self.usage.dead_codes()]
+        return st
 
     def print_stats(self):
         st = self.stats()
@@ -117,4 +132,7 @@ class BatchedAudioDecStreamer:
         print(f"system latency (ms):               {st['latency_ms_mean']:.2f} (max {st['latency_ms_max']:.2f})")
         print(f"underruns / frame drops:           {st['underruns']} / {st['frame_drops']}")
         print(f"payload per stream (kbps):         {st['payload_kbps_per_stream']:.2f}")
+        if "codebook_perplexity" in st:
+            print(f"code perplexity per stage:         {' '.join(f'{v:.1f}' for v in st['codebook_perplexity'])}")
+            print(f"dead codes per stage:              {' '.join(str(v) for v in st['codebook_dead_codes'])}")
         print("#" * 80)

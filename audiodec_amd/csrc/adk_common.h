@@ -62,6 +62,16 @@ __device__ __forceinline__ float act_apply(float x, int act, float slope) {
     return x;
 }
 
+// One straight-through + residual step of the residual VQ on one component (layers/vq_module.py:101-102, 143-144):
+// q' = r + (q - r), r <- r - q'; returns q'.  Every RVQ search kernel (rvq.hip) and the statistics pass that rebuilds the
+// residual chain from the emitted codes (rvq_stats.hip) go through this one function: explicit round-to-nearest operations,
+// nothing contracted, so the rebuilt residuals are the searched ones bit for bit.
+__device__ __forceinline__ float rvq_residual_step(float& r, float q) {
+    const float qp = __fadd_rn(r, __fsub_rn(q, r));
+    r = __fsub_rn(r, qp);
+    return qp;
+}
+
 struct RingMeanArgs {
     const float* src[4]; int src_rows[4], src_cursor[4];
     float* out; int out_rows, out_cursor;

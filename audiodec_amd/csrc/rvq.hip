@@ -131,10 +131,8 @@ __global__ __launch_bounds__(RVQ_THREADS) void rvq_encode_kernel(const float* __
         __syncthreads();
         for (int e = tid; e < RB * dim; e += RVQ_THREADS) {   // straight-through + residual (vq_module.py:101-102,143-144)
             const int rr = e / dim, d = e - rr * dim;
-            const float r = r_sh[rr][d];
-            const float q = E[(size_t)d * size + best_sh[rr]];
-            const float qp = __fadd_rn(r, __fsub_rn(q, r));
-            const float rn = __fsub_rn(r, qp);
+            float rn = r_sh[rr][d];
+            const float qp = rvq_residual_step(rn, E[(size_t)d * size + best_sh[rr]]);
             r_sh[rr][d] = rn;
             r2t_sh[d][rr] = 2.f * rn;
             q_sh[rr][d] = __fadd_rn(q_sh[rr][d], qp);
@@ -235,8 +233,7 @@ __global__ __launch_bounds__(RVQ_THREADS) void rvq_encode_v2_kernel(const float*
         __syncthreads();                                   // B: q visible
         if (owner) {                                       // straight-through + residual (vq_module.py:101-102,143-144)
             const float q = q_sh[wave][lane];
-            const float qp = __fadd_rn(r_reg, __fsub_rn(q, r_reg));
-            r_reg = __fsub_rn(r_reg, qp);
+            const float qp = rvq_residual_step(r_reg, q);
             qsum = __fadd_rn(qsum, qp);
             r2t_sh[lane][wave] = 2.f * r_reg;
             float v = __fmul_rn(r_reg, r_reg);
@@ -363,8 +360,7 @@ __global__ __launch_bounds__(RVQ_THREADS) void rvq_encode_v3_kernel(const float*
         en = enorm[(size_t)(has_next ? st + 1 : st) * SIZE + tid];
         __builtin_amdgcn_sched_barrier(0);
         if (wave == 0) {                                   // straight-through + residual (vq_module.py:101-102,143-144)
-            const float qp = __fadd_rn(r_reg, __fsub_rn(q, r_reg));
-            r_reg = __fsub_rn(r_reg, qp);
+            const float qp = rvq_residual_step(r_reg, q);
             qsum = __fadd_rn(qsum, qp);
             r2_sh[lane] = 2.f * r_reg;
             float s2 = __fmul_rn(r_reg, r_reg);
@@ -493,8 +489,7 @@ __global__ __launch_bounds__(RVQ_THREADS) void rvq_encode_v4_kernel(const float*
         en = enorm[(size_t)(has_next ? st + 1 : st) * SIZE + tid];
         __builtin_amdgcn_sched_barrier(0);
         if (owner) {                                       // straight-through + residual (vq_module.py:101-102,143-144)
-            const float qp = __fadd_rn(r_reg, __fsub_rn(q, r_reg));
-            r_reg = __fsub_rn(r_reg, qp);
+            const float qp = rvq_residual_step(r_reg, q);
             qsum = __fadd_rn(qsum, qp);
             r2_sh[wave >> 1][2 * lane + (wave & 1)] = 2.f * r_reg;
             float s2 = __fmul_rn(r_reg, r_reg);

@@ -2,8 +2,8 @@
 
 ``CausalConv1d`` / ``CausalConvTranspose1d`` expose the reference's constructor arguments and the
 streaming ``inference`` / ``reset_buffer`` methods (conv_layer.py:118-159, 162-200) on top of
-``adk_causal_conv`` with a private state ring; ``ResidualVQ`` exposes ``forward_index`` / ``initial``
-/ ``lookup`` (vq_module.py:136-161) on top of ``adk_rvq_encode`` / ``adk_rvq_lookup``.  The model
+``adk_causal_conv`` with a private state ring; ``ResidualVQ`` exposes ``forward`` / ``forward_index`` / ``initial``
+/ ``lookup`` (vq_module.py:119-161) on top of ``adk_rvq_encode`` / ``adk_rvq_stats`` / ``adk_rvq_lookup``.  The model
 programs (program.py) do not go through these objects -- they exist so single layers can be used and
 tested against the reference's layer classes one to one.
 
@@ -183,7 +183,7 @@ class CausalConvTranspose1d(_CausalBase):
 
 
 class ResidualVQ:
-    """Residual VQ inference (layers/vq_module.py:107-161): forward_index / initial / lookup."""
+    """Residual VQ (layers/vq_module.py:107-161): forward (eval mode) / forward_index / initial / lookup."""
 
     def __init__(self, embeds, device="cuda:0"):
         """embeds: list of the reference's `embed` buffers, each (dim, codebook_size)."""
@@ -195,6 +195,7 @@ class ResidualVQ:
         self.enorm = torch.stack([e.pow(2).sum(0, keepdim=True)[0] for e in emb]).contiguous().to(self.dev)
         self._emb_cpu = emb
         self.codebook = None
+        self._cb_rows = None           # private row-major copy for forward(): lookup() keeps needing initial(), as in the reference
 
     def forward_index(self, x, flatten_idx=False):
         """x (B, T, dim) -> (quantized_out (B, T, dim), indices (n_q, B, T) squeezed at dim 1)."""
@@ -210,6 +211,29 @@ class ResidualVQ:
         if not flatten_idx:
             idx = idx - (torch.arange(self.n_q, device=self.dev) * self.codebook_size).view(-1, 1, 1)
         return zq, idx.squeeze(1)
+
+    def forward(self, x):
+        """ResidualVQ.forward in eval mode (vq_module.py:119-134): x (B, T, dim) -> (quantized_out (B, T, dim), losses (n_q,),
+        perplexities (n_q,)).  quantized_out is forward_index's (the same search); the per-stage commitment loss and code-histogram
+        perplexity come from adk_rvq_stats over the emitted codes.  Needs no initial(): the row-major codes are a private copy."""
+        from . import codebook_usage
+        B, T, D = x.shape
+        xt = x.to(self.dev, torch.float32).contiguous()
+        idx = torch.empty(self.n_q, B * T, dtype=torch.int64, device=self.dev)
+        zq = torch.empty(B, T, D, device=self.dev)
+        native.check(native.lib().adk_rvq_encode(
+            C.c_void_p(xt.data_ptr()), C.c_void_p(self.embed.data_ptr()), C.c_void_p(self.enorm.data_ptr()),
+            C.c_void_p(idx.data_ptr()), C.c_void_p(zq.data_ptr()), B * T, self.n_q, self.dim, self.codebook_size,
+            native.current_stream(self.dev)), "adk_rvq_encode")
+        if self._cb_rows is None:
+            self._cb_rows = codebook_usage.row_major_codebook(self._emb_cpu, self.dev)
+        losses = torch.empty(self.n_q, dtype=torch.float32, device=self.dev)
+        perplexities = torch.empty(self.n_q, dtype=torch.float32, device=self.dev)
+        acc = codebook_usage.accumulator(self.n_q, self.codebook_size, self.dev)
+        codebook_usage.fold(acc, xt.view(B * T, D), self._cb_rows, idx, self.n_q, self.dim, self.codebook_size, losses, perplexities)
+        return zq, losses, perplexities
+
+    __call__ = forward
 
     def initial(self):
         cb = torch.stack([e.transpose(0, 1) for e in self._emb_cpu])

@@ -65,6 +65,8 @@ SYMBOLS = {
     "adk_ring_write": (C.c_int, [_vp, RingView, _vp, _vp, _i32, _i32, _vp]),
     "adk_rvq_encode": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "adk_rvq_lookup": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "adk_rvq_stats_workspace_bytes": (C.c_int64, [_i32, _i32]),
+    "adk_rvq_stats": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "adk_packed_weight_floats_split16": (C.c_int64, [_i32, _i32, _i32]),
     "adk_pack_weights_split16": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "adk_codes_frame_bytes": (C.c_int32, [_i32, _i32]),

@@ -448,10 +448,21 @@ class AutoEncoderStreamGenerator(_StreamBase):
         idx = idx.reshape(self.n_q, B, T)
         return idx.squeeze(1) if B == 1 else idx
 
-    def quantizer_forward(self, z):
+    def quantizer_forward(self, z, return_stats=False):
         """Quantizer.forward in eval mode (quantizer.py:32-35 -> ResidualVQ.forward, vq_module.py:119-134):
-        z (B, code_dim, T) -> zq (B, code_dim, T), the sum of the straight-through stage outputs."""
-        return self._guarded(self._quantizer_forward, (z,), [], 0)
+        z (B, code_dim, T) -> zq (B, code_dim, T), the sum of the straight-through stage outputs.  return_stats=True returns
+        (zq, vqloss (n_q,), perplexity (n_q,)) as Quantizer.forward does: the per-stage commitment loss and code-histogram
+        perplexity of this call's rows (adk_rvq_stats; zq is the same, bit for bit)."""
+        if not return_stats:
+            return self._guarded(self._quantizer_forward, (z,), [], 0)
+        out = self._guarded(self._quantizer_forward_stats, (z,), [], 0)
+        # one flat result [zq | vqloss | perplexity], so that a lazy-guard repair rewrites all three in place; handed out as views
+        log = lazy_guard.log_of(out)
+        flat = lazy_guard.plain(out)
+        B, D, T = lazy_guard.plain(z).shape
+        n = B * T * D
+        parts = (flat[:n].view(B, T, D).transpose(2, 1), flat[n:n + self.n_q], flat[n + self.n_q:])
+        return tuple(lazy_guard.GuardedTensor.wrap(t, log) for t in parts) if log is not None else parts
 
     def _quantizer_forward(self, z):
         dev = self._dev()
@@ -465,6 +476,47 @@ class AutoEncoderStreamGenerator(_StreamBase):
             C.c_void_p(idx.data_ptr()), C.c_void_p(zq.data_ptr()), B * T, self.n_q, self.dim, self.size,
             native.current_stream(dev)), "adk_rvq_encode")
         return zq.transpose(2, 1)
+
+    def _quantizer_forward_stats(self, z):
+        from . import codebook_usage
+        dev = self._dev()
+        embed, enorm = self._quantizer()
+        if self._codebook is None:
+            self.initial()
+        B, D, T = z.shape
+        n = B * T * D
+        zt = z.to(device=dev, dtype=torch.float32).transpose(2, 1).contiguous()
+        idx = torch.empty(self.n_q, B * T, dtype=torch.int64, device=dev)
+        out = torch.empty(n + 2 * self.n_q, dtype=torch.float32, device=dev)
+        native.check(native.lib().adk_rvq_encode(
+            C.c_void_p(zt.data_ptr()), C.c_void_p(embed.data_ptr()), C.c_void_p(enorm.data_ptr()),
+            C.c_void_p(idx.data_ptr()), C.c_void_p(out.data_ptr()), B * T, self.n_q, self.dim, self.size,
+            native.current_stream(dev)), "adk_rvq_encode")
+        # a fresh accumulator per call, zeroed here: a repeat of this call by the lazy guard recomputes the same values
+        acc = codebook_usage.accumulator(self.n_q, self.size, dev)
+        codebook_usage.fold(acc, zt.view(B * T, D), self._codebook, idx, self.n_q, self.dim, self.size,
+                            out[n:n + self.n_q], out[n + self.n_q:])
+        return out
+
+    def forward(self, x):
+        """Generator.forward in eval mode (AudioDec.py:112-120): x (B, C, L) -> (y, zq, z, vqloss, perplexity).
+        A mono model fed C channels runs them as B*C streams, (B, C, L) -> (B', C', L), as the reference reshapes.  The
+        non-streaming forward: needs set_offline(True).  Like the file-level drivers (offline.TestMain.encode) the call carries
+        one stream per batch row (configure(num_streams=B')), starts from reset_buffer() and runs in chunks of max_frames hops.
+        vqloss / perplexity: (n_q,) per-stage commitment loss and code-histogram perplexity over all B' x T rows."""
+        if not self.offline:
+            raise native.NativeError("forward() is the non-streaming Generator.forward: call set_offline(True) first "
+                                     "(encode / quantize / lookup / decode are the streaming calls)")
+        (batch, channel, length) = x.size()
+        if channel != self.input_channels:
+            x = x.reshape(-1, self.input_channels, length)         # (B, C, T) -> (B', C', T)
+        if x.shape[0] != self.num_streams:
+            self.configure(x.shape[0], self.max_frames)
+        self.reset_buffer()
+        z = self.encode(x)
+        zq, vqloss, perplexity = self.quantizer_forward(z, return_stats=True)
+        y = self.decode(zq.transpose(2, 1))
+        return y, zq, z, vqloss, perplexity
 
     def lookup(self, idx):
         """idx (n_q, T) -> zq (1, T, code_dim); (n_q, B, T) -> (B, T, code_dim)  (AudioDec.py:242-243)."""

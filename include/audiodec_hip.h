@@ -198,6 +198,30 @@ int adk_rvq_lookup(const int64_t* idx, const float* codebook, float* zq,
                    int32_t n_rows, int32_t n_q, int32_t dim, int32_t n_codes, void* stream);
 
 /*
+ * Residual VQ statistics: the per-stage commitment loss and code histogram of ResidualVQ.forward / VectorQuantize.forward in
+ * eval mode (layers/vq_module.py:61-88, 119-134), for codes adk_rvq_encode emitted.
+ *   z        [n_rows][dim]           the latent rows given to adk_rvq_encode
+ *   codebook [n_q*size][dim]         row-major codes (the adk_rvq_lookup layout)
+ *   idx      [n_q][n_rows] int64     emitted indices, stage s in [size*s, size*(s+1))
+ * Each row's residual chain is rebuilt with adk_rvq_encode's f32 step (q' = r + (q - r), r <- r - q'), so r_s is the residual
+ * stage s searched.  The call FOLDS into a caller-owned accumulator on the device (zero it to start; nothing is cleared here):
+ *   counts [n_q*size] int64   += the code histogram of every stage (global index order)
+ *   sse    [n_q] double       += sum over rows and components of (q_s - r_s)^2 (f32 difference and square, f64 sum)
+ *   rows   [1] int64          += n_rows
+ * vqloss [n_q] f32 (or NULL) = sse / (rows * dim) and perplexity [n_q] f32 (or NULL) = exp(-sum_k p_k log(p_k + 1e-10)) with
+ * p_k = count_k / rows in f32, both from the totals AFTER this call's fold (NaN while rows == 0).  n_rows == 0 folds nothing and
+ * only writes what is asked for.  workspace: adk_rvq_stats_workspace_bytes(n_rows, n_q) bytes, 8-byte aligned, any contents,
+ * unused once the call's work has finished (NULL when that size is 0).  Bitwise reproducible: float sums go through
+ * per-workgroup slabs in a fixed order.  Calls on one accumulator must be ordered (one stream).  An index outside its stage
+ * counts nothing, reads that stage's first code and raises bit 0 of adk_debug_flags().  Limits: dim <= 128, n_q <= 16,
+ * n_q*size < 2^31.  Every argument is checked before any HIP call (ADK_ERR_ARG).
+ */
+int64_t adk_rvq_stats_workspace_bytes(int32_t n_rows, int32_t n_q);
+int adk_rvq_stats(const float* z, const float* codebook, const int64_t* idx, int32_t n_rows, int32_t n_q, int32_t dim,
+                  int32_t size, int64_t* counts, double* sse, int64_t* rows, void* workspace, float* vqloss,
+                  float* perplexity, void* stream);
+
+/*
  * Bit-packed code wire format (the reference passes the int64 index tensor through a
  * queue.Queue, bin/stream.py:224,230, and never serialises it).  One frame of one stream = n_q codes of
  * `bits` bits, LSB-first: code q (= emitted index - size*q) occupies bits [q*bits, (q+1)*bits) of the
