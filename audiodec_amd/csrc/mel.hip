@@ -1,0 +1,336 @@
+// Log-mel spectrogram and mel L1 distance: MelSpectrogram.forward / MultiMelSpectrogramLoss.forward (losses/mel_loss.py:19-156)
+// for one resolution, as torch.stft's defaults make it (center=True, reflect padding of n_fft/2, no normalisation, one-sided):
+//   frame f of signal s = x[s][f*hop - n_fft/2 + j] (reflected at both ends) * window_centred[j],   j < n_fft,  1 + T/hop frames
+//   amp[k] = sqrt(clamp(re^2 + im^2, eps)),  k <= n_fft/2;   mel[m] = clamp(sum_k amp[k] melmat[k][m], eps);   out = log(mel)
+// One frame is one wave and never leaves it: the frame lives in LDS (n_fft floats = n_fft/2 complex), the n_fft-point real FFT
+// is an n_fft/2-point complex radix-2 decimation-in-frequency FFT (natural order in, bit-reversed order out, read back through
+// the bit reversal) plus the even/odd untangle.  Twiddles are exp(-2 pi i k / n_fft) evaluated in f64 and rounded to f32,
+// built once per workgroup.  The mel filters come from a sparse table (one contiguous bin range per filter), summed in bin
+// order.  A workgroup is one wave, so its barriers are wave-local; it loops over frames with no other synchronisation.
+//   logmel mode:   blocks of MEL_FB frames of one signal are staged in LDS, then stored as coalesced runs of (n_mels, frames)
+//   distance mode: |logmel(a) - logmel(b)| in f32, summed per lane in f64, never stored; per-workgroup f64 partials in a slab
+//                  and a fixed-order finalize launch (no float atomics), so the sum is bitwise reproducible run to run.
+#include "adk_common.h"
+
+namespace adk {
+
+constexpr int MEL_THREADS = 64;                        // one wave per workgroup
+constexpr int MEL_MAX_MELS = 256;
+constexpr int MEL_MPL = MEL_MAX_MELS / 64;             // mel filters per lane
+constexpr int MEL_FB = 16;                             // logmel mode: frames per staged block
+constexpr int MEL_MAX_WG = 2048;
+constexpr int MEL_LOG_E = 0, MEL_LOG_2 = 2, MEL_LOG_10 = 10;
+
+static long long mel_frames(int n_samples, int hop) { return 1 + (long long)n_samples / hop; }
+
+static int mel_distance_workgroups(long long n_frames_total) {
+    return (int)std::min<long long>(std::max<long long>(n_frames_total, 1), MEL_MAX_WG);
+}
+
+struct MelArgs {
+    int n_samples, hop, win_length, lpad, n_mels, n_weights, log_base;
+    long long frames;
+    float eps;
+    const float* window;
+    const int* fb_range;                               // [n_mels][3]: first bin, bin count, offset into fb_weight
+    const float* fb_weight;
+};
+
+__device__ __forceinline__ float mel_log(float v, int base) {
+    return base == MEL_LOG_10 ? log10f(v) : base == MEL_LOG_2 ? log2f(v) : logf(v);
+}
+
+// clamp(v, min=eps) as torch.clamp: NaN stays NaN
+__device__ __forceinline__ float clamp_min(float v, float eps) { return v < eps ? eps : v; }
+
+template <int LOG2N>
+__device__ void build_twiddles(float2* tw) {
+    constexpr int NFFT = 2 << LOG2N, N = 1 << LOG2N;
+    for (int k = threadIdx.x; k <= N; k += MEL_THREADS) {
+        double s, c;
+        sincospi(2.0 * (double)k / (double)NFFT, &s, &c);
+        tw[k] = make_float2((float)c, (float)(-s));
+    }
+}
+
+// Log-mels of frame f of signal x into mels[i] = filter lane + 64 i.  buf: n_fft floats of LDS.  Ends with a barrier, so the
+// caller may reuse buf at once.
+template <int LOG2N>
+__device__ void frame_logmel(const float* __restrict__ x, long long f, const MelArgs& a, float* buf, const float2* tw,
+                             float (&mels)[MEL_MPL]) {
+    constexpr int NFFT = 2 << LOG2N, N = 1 << LOG2N, HALF = NFFT / 2;
+    constexpr int PER = (N + 1 + MEL_THREADS - 1) / MEL_THREADS;
+    const int lane = threadIdx.x;
+    const long long t0 = f * a.hop - HALF;
+    const int T = a.n_samples;
+    // load: reflect padding and the centred zero-padded window at load time; sample j is float j of the complex buffer
+#pragma unroll 4
+    for (int j = lane; j < NFFT; j += MEL_THREADS) {
+        long long t = t0 + j;
+        t = t < 0 ? -t : t;
+        t = t >= T ? 2LL * (T - 1) - t : t;
+        const int jw = j - a.lpad;
+        const float w = (jw >= 0 && jw < a.win_length) ? a.window[jw] : 0.f;
+        buf[j] = __fmul_rn(x[t], w);
+    }
+    __syncthreads();
+    float2* z = reinterpret_cast<float2*>(buf);
+    // radix-2 DIF: stage with half-span h pairs (i, i + h), twiddle exp(-2 pi i pos / 2h) = tw[pos * N / h]
+#pragma unroll
+    for (int lh = LOG2N - 1; lh >= 0; --lh) {
+        const int h = 1 << lh;
+#pragma unroll 4
+        for (int b = lane; b < N / 2; b += MEL_THREADS) {
+            const int pos = b & (h - 1);
+            const int i = ((b - pos) << 1) + pos;
+            const float2 u = z[i], v = z[i + h];
+            const float2 w = tw[pos << (LOG2N - lh)];
+            const float dx = u.x - v.x, dy = u.y - v.y;
+            z[i] = make_float2(u.x + v.x, u.y + v.y);
+            z[i + h] = make_float2(dx * w.x - dy * w.y, dx * w.y + dy * w.x);
+        }
+        __syncthreads();
+    }
+    // untangle: X[k] = (Z[k] + conj Z[N-k]) / 2 + tw[k] (Z[k] - conj Z[N-k]) / 2i,  Z[k] at bit-reversed address
+    float amp[PER];
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+        const int k = lane + q * MEL_THREADS;
+        amp[q] = 0.f;
+        if (k <= N) {
+            const int k1 = k & (N - 1), k2 = (N - k) & (N - 1);
+            const float2 A = z[__builtin_bitreverse32((unsigned)k1) >> (32 - LOG2N)];
+            const float2 B = z[__builtin_bitreverse32((unsigned)k2) >> (32 - LOG2N)];
+            const float ex = 0.5f * (A.x + B.x), ey = 0.5f * (A.y - B.y);
+            const float ox = 0.5f * (A.y + B.y), oy = -0.5f * (A.x - B.x);
+            const float2 w = tw[k];
+            const float re = ex + (ox * w.x - oy * w.y);
+            const float im = ey + (ox * w.y + oy * w.x);
+            amp[q] = sqrtf(clamp_min(re * re + im * im, a.eps));
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+        const int k = lane + q * MEL_THREADS;
+        if (k <= N) buf[k] = amp[q];
+    }
+    __syncthreads();
+    // mel filters: lane sums filter m = lane + 64 i over its bin range, in bin order
+#pragma unroll
+    for (int i = 0; i < MEL_MPL; ++i) {
+        const int m = lane + i * MEL_THREADS;
+        float s = 0.f;
+        if (m < a.n_mels) {
+            const int first = a.fb_range[3 * m], count = a.fb_range[3 * m + 1], off = a.fb_range[3 * m + 2];
+            const int lo = max(first, 0), hi = off < 0 ? lo : min(min(first + count, N + 1), a.n_weights - off + first);
+            for (int k = lo; k < hi; ++k) s = fmaf(a.fb_weight[off + (k - first)], buf[k], s);
+        }
+        mels[i] = mel_log(clamp_min(s, a.eps), a.log_base);
+    }
+    __syncthreads();
+}
+
+template <int LOG2N>
+__global__ __launch_bounds__(MEL_THREADS) void logmel_kernel(const float* __restrict__ x, int n_signals, MelArgs a,
+                                                             float* __restrict__ out) {
+    constexpr int NFFT = 2 << LOG2N, N = 1 << LOG2N;
+    extern __shared__ float lds[];
+    float2* tw = reinterpret_cast<float2*>(lds);                  // N + 1 twiddles
+    float* buf = lds + 2 * (N + 2);                              // NFFT floats
+    float* stage = buf + NFFT;                                   // [n_mels][MEL_FB]
+    build_twiddles<LOG2N>(tw);
+    __syncthreads();
+    const int lane = threadIdx.x;
+    const long long blocks = (a.frames + MEL_FB - 1) / MEL_FB;
+    const long long items = blocks * n_signals;
+    for (long long it = blockIdx.x; it < items; it += gridDim.x) {
+        const int s = (int)(it / blocks);
+        const long long f0 = (it - (long long)s * blocks) * MEL_FB;
+        const int nb = (int)min((long long)MEL_FB, a.frames - f0);
+        const float* xs = x + (size_t)s * a.n_samples;
+        for (int j = 0; j < nb; ++j) {
+            float mels[MEL_MPL];
+            frame_logmel<LOG2N>(xs, f0 + j, a, buf, tw, mels);
+#pragma unroll
+            for (int i = 0; i < MEL_MPL; ++i) {
+                const int m = lane + i * MEL_THREADS;
+                if (m < a.n_mels) stage[m * MEL_FB + j] = mels[i];
+            }
+        }
+        __syncthreads();
+        float* os = out + (size_t)s * a.n_mels * a.frames + f0;
+        for (int e = lane; e < a.n_mels * nb; e += MEL_THREADS) {
+            const int m = e / nb, j = e - m * nb;
+            os[(size_t)m * a.frames + j] = stage[m * MEL_FB + j];
+        }
+        __syncthreads();
+    }
+}
+
+template <int LOG2N>
+__global__ __launch_bounds__(MEL_THREADS) void mel_distance_kernel(const float* __restrict__ xa, const float* __restrict__ xb,
+                                                                   int n_signals, MelArgs a, double* __restrict__ partial) {
+    constexpr int N = 1 << LOG2N;
+    extern __shared__ float lds[];
+    float2* tw = reinterpret_cast<float2*>(lds);
+    float* buf = lds + 2 * (N + 2);
+    build_twiddles<LOG2N>(tw);
+    __syncthreads();
+    const int lane = threadIdx.x;
+    const long long items = a.frames * n_signals;
+    double acc = 0.0;
+    for (long long it = blockIdx.x; it < items; it += gridDim.x) {
+        const int s = (int)(it / a.frames);
+        const long long f = it - (long long)s * a.frames;
+        float ma[MEL_MPL], mb[MEL_MPL];
+        frame_logmel<LOG2N>(xa + (size_t)s * a.n_samples, f, a, buf, tw, ma);
+        frame_logmel<LOG2N>(xb + (size_t)s * a.n_samples, f, a, buf, tw, mb);
+#pragma unroll
+        for (int i = 0; i < MEL_MPL; ++i)
+            if (lane + i * MEL_THREADS < a.n_mels) acc += (double)fabsf(__fsub_rn(ma[i], mb[i]));
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    if (lane == 0) partial[blockIdx.x] = acc;
+}
+
+// One wave: folds the slab into sum (workgroups in a fixed order), adds count, writes loss from the totals.
+__global__ __launch_bounds__(MEL_THREADS) void mel_distance_finalize_kernel(const double* __restrict__ partial, int n_wg,
+                                                                            long long n_values, double* __restrict__ sum,
+                                                                            long long* __restrict__ count, float* __restrict__ loss) {
+    const int lane = threadIdx.x;
+    double t = 0.0;
+    for (int b = lane; b < n_wg; b += MEL_THREADS) t += partial[b];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) t += __shfl_xor(t, off, 64);
+    if (lane == 0) {
+        const double acc = sum[0] + t;
+        const long long n = count[0] + n_values;
+        sum[0] = acc;
+        count[0] = n;
+        if (loss) loss[0] = n > 0 ? (float)(acc / (double)n) : __builtin_nanf("");
+    }
+}
+
+template <int LOG2N>
+static size_t mel_lds_bytes(int n_mels, bool stage) {
+    constexpr int N = 1 << LOG2N;
+    return sizeof(float) * (2 * (N + 2) + 2 * N + (stage ? (size_t)n_mels * MEL_FB : 0));
+}
+
+static int check_common(const char* fn, int n_signals, int n_samples, int n_fft, int hop, const float* window, int win_length,
+                        const int32_t* fb_range, const float* fb_weight, int n_weights, int n_mels, int log_base) {
+    const std::string f(fn);
+    if (n_fft < 256 || n_fft > 4096 || (n_fft & (n_fft - 1)))
+        return fail(ADK_ERR_ARG, f + ": n_fft must be a power of two in [256, 4096]");
+    if (hop <= 0) return fail(ADK_ERR_ARG, f + ": need hop > 0");
+    if (win_length <= 0 || win_length > n_fft) return fail(ADK_ERR_ARG, f + ": need 0 < win_length <= n_fft");
+    if (n_signals < 0) return fail(ADK_ERR_ARG, f + ": need n_signals >= 0");
+    if (n_samples <= n_fft / 2)
+        return fail(ADK_ERR_ARG, f + ": reflect padding needs n_samples > n_fft / 2");
+    if (n_mels <= 0 || n_mels > MEL_MAX_MELS) return fail(ADK_ERR_ARG, f + ": need 0 < n_mels <= 256");
+    if (n_weights <= 0) return fail(ADK_ERR_ARG, f + ": need n_weights > 0");
+    if (log_base != MEL_LOG_E && log_base != MEL_LOG_2 && log_base != MEL_LOG_10)
+        return fail(ADK_ERR_ARG, f + ": log_base must be 0 (natural), 2 or 10");
+    if (!window || !fb_range || !fb_weight) return fail(ADK_ERR_ARG, f + ": null pointer");
+    if ((reinterpret_cast<uintptr_t>(window) | reinterpret_cast<uintptr_t>(fb_range) | reinterpret_cast<uintptr_t>(fb_weight)) & 3)
+        return fail(ADK_ERR_ARG, f + ": window/fb_range/fb_weight must be 4-byte aligned");
+    return ADK_OK;
+}
+
+static MelArgs make_args(int n_samples, int n_fft, int hop, const float* window, int win_length, const int32_t* fb_range,
+                         const float* fb_weight, int n_weights, int n_mels, int log_base, float eps) {
+    MelArgs a;
+    a.n_samples = n_samples; a.hop = hop; a.win_length = win_length; a.lpad = (n_fft - win_length) / 2;
+    a.n_mels = n_mels; a.n_weights = n_weights; a.log_base = log_base;
+    a.frames = mel_frames(n_samples, hop); a.eps = eps;
+    a.window = window; a.fb_range = reinterpret_cast<const int*>(fb_range); a.fb_weight = fb_weight;
+    return a;
+}
+
+template <int LOG2N>
+static void launch_logmel(const float* x, int n_signals, const MelArgs& a, float* out, hipStream_t s) {
+    const long long items = (a.frames + MEL_FB - 1) / MEL_FB * n_signals;
+    const int n_wg = (int)std::min<long long>(items, 4 * MEL_MAX_WG);
+    hipLaunchKernelGGL(logmel_kernel<LOG2N>, dim3(n_wg), dim3(MEL_THREADS), mel_lds_bytes<LOG2N>(a.n_mels, true), s, x, n_signals, a, out);
+}
+
+template <int LOG2N>
+static void launch_distance(const float* xa, const float* xb, int n_signals, const MelArgs& a, int n_wg, double* partial, hipStream_t s) {
+    hipLaunchKernelGGL(mel_distance_kernel<LOG2N>, dim3(n_wg), dim3(MEL_THREADS), mel_lds_bytes<LOG2N>(a.n_mels, false), s,
+                       xa, xb, n_signals, a, partial);
+}
+
+static int log2_of(int n) { int l = 0; while ((1 << l) < n) ++l; return l; }
+
+}  // namespace adk
+
+using namespace adk;
+
+extern "C" int64_t adk_mel_workspace_bytes(int32_t n_signals, int32_t n_samples, int32_t n_fft, int32_t hop) {
+    if (n_signals < 0 || n_samples <= 0 || hop <= 0 || n_fft <= 0)
+        return fail(ADK_ERR_ARG, "adk_mel_workspace_bytes: need n_signals >= 0, n_samples > 0, hop > 0, n_fft > 0");
+    if (n_signals == 0) return 0;
+    return (int64_t)mel_distance_workgroups(mel_frames(n_samples, hop) * n_signals) * (int64_t)sizeof(double);
+}
+
+extern "C" int adk_logmel(const float* x, int32_t n_signals, int32_t n_samples, int32_t n_fft, int32_t hop, const float* window,
+                          int32_t win_length, const int32_t* fb_range, const float* fb_weight, int32_t n_weights, int32_t n_mels,
+                          int32_t log_base, float eps, float* out, void* stream) {
+    int rc = check_common("adk_logmel", n_signals, n_samples, n_fft, hop, window, win_length, fb_range, fb_weight, n_weights,
+                          n_mels, log_base);
+    if (rc != ADK_OK) return rc;
+    if (n_signals > 0 && (!x || !out)) return fail(ADK_ERR_ARG, "adk_logmel: null pointer");
+    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 3)
+        return fail(ADK_ERR_ARG, "adk_logmel: x/out must be 4-byte aligned");
+    if (n_signals == 0) return ADK_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DeviceGuard guard(device_of(out));
+    const MelArgs a = make_args(n_samples, n_fft, hop, window, win_length, fb_range, fb_weight, n_weights, n_mels, log_base, eps);
+    switch (log2_of(n_fft) - 1) {
+        case 7: launch_logmel<7>(x, n_signals, a, out, s); break;
+        case 8: launch_logmel<8>(x, n_signals, a, out, s); break;
+        case 9: launch_logmel<9>(x, n_signals, a, out, s); break;
+        case 10: launch_logmel<10>(x, n_signals, a, out, s); break;
+        default: launch_logmel<11>(x, n_signals, a, out, s); break;
+    }
+    ADK_HIP_CHECK(hipGetLastError());
+    return ADK_OK;
+}
+
+extern "C" int adk_mel_distance(const float* a_sig, const float* b_sig, int32_t n_signals, int32_t n_samples, int32_t n_fft,
+                                int32_t hop, const float* window, int32_t win_length, const int32_t* fb_range,
+                                const float* fb_weight, int32_t n_weights, int32_t n_mels, int32_t log_base, float eps,
+                                double* sum, int64_t* count, void* workspace, float* loss, void* stream) {
+    int rc = check_common("adk_mel_distance", n_signals, n_samples, n_fft, hop, window, win_length, fb_range, fb_weight,
+                          n_weights, n_mels, log_base);
+    if (rc != ADK_OK) return rc;
+    if (!sum || !count) return fail(ADK_ERR_ARG, "adk_mel_distance: null accumulator pointer");
+    if (n_signals > 0 && (!a_sig || !b_sig || !workspace)) return fail(ADK_ERR_ARG, "adk_mel_distance: null pointer");
+    if ((reinterpret_cast<uintptr_t>(sum) | reinterpret_cast<uintptr_t>(count) | reinterpret_cast<uintptr_t>(workspace)) & 7)
+        return fail(ADK_ERR_ARG, "adk_mel_distance: sum/count/workspace must be 8-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(a_sig) | reinterpret_cast<uintptr_t>(b_sig) | reinterpret_cast<uintptr_t>(loss)) & 3)
+        return fail(ADK_ERR_ARG, "adk_mel_distance: a/b/loss must be 4-byte aligned");
+    if (n_signals == 0 && !loss) return ADK_OK;        // nothing to fold, nothing asked for
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DeviceGuard guard(device_of(sum));
+    const MelArgs a = make_args(n_samples, n_fft, hop, window, win_length, fb_range, fb_weight, n_weights, n_mels, log_base, eps);
+    const long long total = a.frames * n_signals;
+    const int n_wg = n_signals > 0 ? mel_distance_workgroups(total) : 0;
+    double* partial = static_cast<double*>(workspace);
+    if (n_signals > 0) {
+        switch (log2_of(n_fft) - 1) {
+            case 7: launch_distance<7>(a_sig, b_sig, n_signals, a, n_wg, partial, s); break;
+            case 8: launch_distance<8>(a_sig, b_sig, n_signals, a, n_wg, partial, s); break;
+            case 9: launch_distance<9>(a_sig, b_sig, n_signals, a, n_wg, partial, s); break;
+            case 10: launch_distance<10>(a_sig, b_sig, n_signals, a, n_wg, partial, s); break;
+            default: launch_distance<11>(a_sig, b_sig, n_signals, a, n_wg, partial, s); break;
+        }
+        ADK_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(mel_distance_finalize_kernel, dim3(1), dim3(MEL_THREADS), 0, s, partial, n_wg,
+                       total * (long long)n_mels, sum, reinterpret_cast<long long*>(count), loss);
+    ADK_HIP_CHECK(hipGetLastError());
+    return ADK_OK;
+}

@@ -1,0 +1,293 @@
+"""Mel-spectrogram loss on the device: the reference's evaluation metric (adk_logmel, adk_mel_distance).
+
+Mirrors ``losses/mel_loss.py``: ``MelSpectrogram`` (lines 19-94) and ``MultiMelSpectrogramLoss`` (lines 97-156), which the
+reference's trainers build from ``config['mel_loss_params']`` (codecTrain.py:202-205) and use as the metric loss
+(trainer/trainerGAN.py:214-241).  Every shipped config enables it (``use_mel_loss: true``) and nothing else of the metric.
+
+The filter bank is ``librosa.filters.mel(sr, n_fft, n_mels, fmin, fmax)`` with librosa's defaults (Slaney mel scale, Slaney
+area normalisation, float32), restated here in NumPy; librosa is not a dependency.  Each resolution runs one HIP kernel:
+framing with reflect padding, an n_fft-point real FFT, the mel projection from a sparse filter table, the log and -- for the
+loss -- the L1 sum, folded into an f64 accumulator on the device without ever writing the log-mels.
+
+Forward only: an input that requires grad while grad is enabled raises NotImplementedError.
+"""
+import ctypes as C
+import math
+
+import numpy as np
+import torch
+
+from . import lazy_guard, native
+
+_LOG_BASES = {None: 0, 2.0: 2, 10.0: 10}
+
+
+# ---- librosa.filters.mel with its defaults (htk=False, norm='slaney', dtype=float32) ----
+def hz_to_mel(freq):
+    """Slaney mel scale: linear below 1 kHz (200/3 Hz per mel), logarithmic above (1000 Hz = 15 mel, step ln(6.4)/27)."""
+    f = np.asarray(freq, np.float64)
+    f_sp, min_log_hz, min_log_mel, logstep = 200.0 / 3, 1000.0, 15.0, math.log(6.4) / 27.0
+    return np.where(f >= min_log_hz, min_log_mel + np.log(np.maximum(f, min_log_hz) / min_log_hz) / logstep, f / f_sp)
+
+
+def mel_to_hz(mels):
+    m = np.asarray(mels, np.float64)
+    f_sp, min_log_hz, min_log_mel, logstep = 200.0 / 3, 1000.0, 15.0, math.log(6.4) / 27.0
+    return np.where(m >= min_log_mel, min_log_hz * np.exp(logstep * (m - min_log_mel)), f_sp * m)
+
+
+def mel_filterbank(sr, n_fft, n_mels=128, fmin=0.0, fmax=None):
+    """(n_mels, 1 + n_fft // 2) float32: the triangles are computed in f64 and stored into a float32 array, then scaled by the
+    f64 Slaney norm 2 / (f[m+2] - f[m]) in place, as librosa does."""
+    fmax = sr / 2.0 if fmax is None else fmax
+    weights = np.zeros((n_mels, 1 + n_fft // 2), np.float32)
+    fftfreqs = np.fft.rfftfreq(n=n_fft, d=1.0 / sr)
+    mel_f = mel_to_hz(np.linspace(hz_to_mel(fmin), hz_to_mel(fmax), n_mels + 2))
+    fdiff = np.diff(mel_f)
+    ramps = np.subtract.outer(mel_f, fftfreqs)
+    for i in range(n_mels):
+        lower = -ramps[i] / fdiff[i]
+        upper = ramps[i + 2] / fdiff[i + 1]
+        weights[i] = np.maximum(0, np.minimum(lower, upper))
+    enorm = 2.0 / (mel_f[2:n_mels + 2] - mel_f[:n_mels])
+    weights *= enorm[:, np.newaxis]
+    return weights
+
+
+def sparse_filters(melmat):
+    """(n_mels, bins) -> (range int32 [n_mels][3] = first bin, count, offset; weights float32): one contiguous bin range per
+    filter, from its first to its last nonzero weight (zeros inside the range are kept)."""
+    rng, ws, off = [], [], 0
+    for row in np.asarray(melmat, np.float32):
+        nz = np.nonzero(row)[0]
+        first, count = (int(nz[0]), int(nz[-1] - nz[0] + 1)) if nz.size else (0, 0)
+        rng.append((first, count, off))
+        ws.append(row[first:first + count])
+        off += count
+    w = np.concatenate(ws) if off else np.zeros(1, np.float32)
+    return np.asarray(rng, np.int32), np.ascontiguousarray(w, np.float32)
+
+
+def num_frames(n_samples, hop_size):
+    """Frames of torch.stft(center=True): 1 + T // hop."""
+    return 1 + int(n_samples) // int(hop_size)
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _settled(t):
+    lg = lazy_guard.log_of(t)
+    if lg is not None:
+        lg.settle()
+    return lazy_guard.plain(t)
+
+
+def _no_grad_inputs(*ts):
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in ts):
+        raise NotImplementedError("the HIP mel-spectrogram loss is forward only: run it under torch.no_grad() or detach the inputs")
+
+
+def _signals(x, device):
+    """(B, T) or (B, C, T) -> contiguous float32 (B*C, T) on `device` (MelSpectrogram.forward's reshape)."""
+    if x.dim() == 3:
+        x = x.reshape(-1, x.size(2))
+    if x.dim() != 2:
+        raise ValueError(f"expected a (B, T) or (B, C, T) waveform, got shape {tuple(x.shape)}")
+    return x.to(device=device, dtype=torch.float32).contiguous()
+
+
+class MelSpectrogram:
+    """losses/mel_loss.py:19-94 on the HIP path.  Same arguments and defaults.
+
+    As in the reference, ``center``, ``normalized`` and ``onesided`` are accepted and stored but IGNORED: its torch.stft call
+    passes none of them, so torch's defaults always apply -- center=True with reflect padding of fft_size // 2, no
+    normalisation, a one-sided spectrum.  Reflect padding needs T > fft_size // 2 (torch raises otherwise; so does this).
+    Only ``window="hann_window"`` and power-of-two ``fft_size`` in [256, 4096] are implemented."""
+
+    def __init__(self, fs=22050, fft_size=1024, hop_size=256, win_length=None, window="hann_window", num_mels=80, fmin=80,
+                 fmax=7600, center=True, normalized=False, onesided=True, eps=1e-10, log_base=10.0, device=None):
+        self.fft_size = int(fft_size)
+        self.hop_size = int(hop_size)
+        self.win_length = int(win_length) if win_length is not None else self.fft_size
+        self.center, self.normalized, self.onesided = center, normalized, onesided       # stored, ignored (see above)
+        self.eps = eps
+        self.log_base = log_base
+        if log_base not in _LOG_BASES:
+            raise ValueError(f"log_base: {log_base} is not supported.")
+        if window != "hann_window":
+            raise NotImplementedError(f"window {window!r}: only 'hann_window' is implemented on the HIP path")
+        n = self.fft_size
+        if n < 256 or n > 4096 or n & (n - 1):
+            raise NotImplementedError(f"fft_size {n}: the HIP path implements powers of two from 256 to 4096")
+        if self.hop_size <= 0 or not 0 < self.win_length <= n:
+            raise ValueError(f"need hop_size > 0 and 0 < win_length <= fft_size, got {self.hop_size}, {self.win_length}")
+        self.num_mels = int(num_mels)
+        if not 0 < self.num_mels <= 256:
+            raise NotImplementedError(f"num_mels {num_mels}: the HIP path implements 1 to 256 mel bands")
+        fmin = 0 if fmin is None else fmin
+        fmax = fs / 2 if fmax is None else fmax
+        self.melmat = mel_filterbank(fs, n, self.num_mels, fmin, fmax)          # (n_mels, bins), librosa's layout
+        self.window = torch.hann_window(self.win_length)
+        self._range, self._weights = sparse_filters(self.melmat)
+        self._dev = None
+        if device is not None:
+            self.to(device)
+
+    def to(self, device):
+        dev = torch.device(device)
+        native.require_gpu(dev)
+        if self._dev != dev:
+            self._dev = dev
+            self._window_d = self.window.to(dev)
+            self._range_d = torch.from_numpy(self._range).to(dev)
+            self._weights_d = torch.from_numpy(self._weights).to(dev)
+        return self
+
+    def _device_for(self, x):
+        if self._dev is None:
+            self.to(x.device if x.device.type == "cuda" else torch.device("cuda", torch.cuda.current_device()))
+        return self._dev
+
+    def num_frames(self, n_samples):
+        return num_frames(n_samples, self.hop_size)
+
+    def check_length(self, n_samples):
+        if n_samples <= self.fft_size // 2:
+            raise ValueError(f"input length {n_samples}: reflect padding of fft_size // 2 = {self.fft_size // 2} needs more "
+                             f"than {self.fft_size // 2} samples (torch.stft raises for it too)")
+
+    def _args(self):
+        return (self.fft_size, self.hop_size, _ptr(self._window_d), self.win_length, _ptr(self._range_d), _ptr(self._weights_d),
+                int(self._weights.size), self.num_mels, _LOG_BASES[self.log_base], float(self.eps))
+
+    def forward(self, x):
+        """x (B, T) or (B, C, T) -> log-mel (B*C, num_mels, frames) float32 on the device.  Does not synchronise."""
+        _no_grad_inputs(x)
+        x = _settled(x)
+        self.check_length(x.shape[-1])
+        dev = self._device_for(x)
+        xs = _signals(x, dev)
+        n, T = xs.shape
+        out = torch.empty(n, self.num_mels, self.num_frames(T), dtype=torch.float32, device=dev)
+        n_fft, hop, win, wl, rng, wts, nw, nm, lb, eps = self._args()
+        native.check(native.lib().adk_logmel(_ptr(xs), n, T, n_fft, hop, win, wl, rng, wts, nw, nm, lb, eps, _ptr(out),
+                                             native.current_stream(dev)), "adk_logmel")
+        return out
+
+    __call__ = forward
+
+    def fold(self, y_hat, y, sum_, count, loss=None):
+        """adk_mel_distance: sum_ (float64 [1]) += sum |logmel(y_hat) - logmel(y)|, count (int64 [1]) += elements; loss (float32
+        [1] or None) = sum_ / count after the fold.  y_hat, y: contiguous float32 (n, T) on this module's device."""
+        dev = self._dev
+        n, T = (int(y.shape[0]), int(y.shape[1])) if y is not None else (0, self.fft_size)
+        lib = native.lib()
+        ws_bytes = int(lib.adk_mel_workspace_bytes(n, T, self.fft_size, self.hop_size))
+        if ws_bytes < 0:
+            native.check(ws_bytes, "adk_mel_workspace_bytes")
+        ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.float64, device=dev) if ws_bytes else None
+        n_fft, hop, win, wl, rng, wts, nw, nm, lb, eps = self._args()
+        native.check(lib.adk_mel_distance(_ptr(y_hat), _ptr(y), n, T, n_fft, hop, win, wl, rng, wts, nw, nm, lb, eps,
+                                          _ptr(sum_), _ptr(count), _ptr(ws), _ptr(loss), native.current_stream(dev)),
+                     "adk_mel_distance")
+
+
+class MultiMelSpectrogramLoss:
+    """losses/mel_loss.py:97-156 on the HIP path: mean over resolutions of F.l1_loss(f(y_hat), f(y)).  Same arguments and
+    defaults; ``forward(y_hat, y)`` returns a 0-d float32 tensor on the device without synchronising."""
+
+    def __init__(self, fs=22050, fft_sizes=[1024, 2048, 512], hop_sizes=[120, 240, 50], win_lengths=[600, 1200, 240],
+                 window="hann_window", num_mels=80, fmin=80, fmax=7600, center=True, normalized=False, onesided=True, eps=1e-10,
+                 log_base=10.0, device=None):
+        assert len(fft_sizes) == len(hop_sizes) == len(win_lengths)
+        self.mel_transfers = [MelSpectrogram(fs=fs, fft_size=f, hop_size=h, win_length=w, window=window, num_mels=num_mels,
+                                             fmin=fmin, fmax=fmax, center=center, normalized=normalized, onesided=onesided,
+                                             eps=eps, log_base=log_base, device=device)
+                              for f, h, w in zip(fft_sizes, hop_sizes, win_lengths)]
+
+    def to(self, device):
+        for f in self.mel_transfers:
+            f.to(device)
+        return self
+
+    @property
+    def device(self):
+        return self.mel_transfers[0]._dev
+
+    def prepare(self, y_hat, y):
+        """Settled, validated, contiguous float32 (n, T) signals on the loss's device."""
+        _no_grad_inputs(y_hat, y)
+        y_hat, y = _settled(y_hat), _settled(y)
+        if tuple(y_hat.shape) != tuple(y.shape):
+            raise ValueError(f"y_hat {tuple(y_hat.shape)} and y {tuple(y.shape)} must have the same shape")
+        for f in self.mel_transfers:
+            f.check_length(y.shape[-1])
+        dev = self.mel_transfers[0]._device_for(y)
+        self.to(dev)
+        return _signals(y_hat, dev), _signals(y, dev)
+
+    def forward(self, y_hat, y):
+        a, b = self.prepare(y_hat, y)
+        dev = self.device
+        R = len(self.mel_transfers)
+        sums = torch.zeros(R, dtype=torch.float64, device=dev)
+        counts = torch.zeros(R, dtype=torch.int64, device=dev)
+        losses = torch.empty(R, dtype=torch.float32, device=dev)
+        for r, f in enumerate(self.mel_transfers):
+            f.fold(a, b, sums[r:r + 1], counts[r:r + 1], losses[r:r + 1])
+        if R == 1:
+            return losses[0]
+        mel_loss = losses[0]
+        for r in range(1, R):                       # mel_loss += l1 per resolution, then / R, in f32 as the reference
+            mel_loss = mel_loss + losses[r]
+        return mel_loss / R
+
+    __call__ = forward
+
+
+class MelDistance:
+    """The mel-spectrogram loss of a config's ``mel_loss_params``, accumulated on the device over any number of batches.
+
+    ``update(y_hat, y)`` folds the per-resolution L1 sums and element counts without synchronising (lazy-guard results are
+    settled first).  ``value()`` is the mean over resolutions of (sum / count) in f64 -- the loss of all folded batches as one
+    batch; ``count()`` the elements folded per resolution; ``reset()`` zeroes the totals.  ``value()`` and ``count()``
+    synchronise."""
+
+    def __init__(self, loss_params, device):
+        self.loss = MultiMelSpectrogramLoss(**dict(loss_params), device=device)
+        self.device = self.loss.device
+        R = len(self.loss.mel_transfers)
+        self._sum = torch.zeros(R, dtype=torch.float64, device=self.device)
+        self._count = torch.zeros(R, dtype=torch.int64, device=self.device)
+
+    def reset(self):
+        self._sum.zero_()
+        self._count.zero_()
+        return self
+
+    def update(self, y_hat, y):
+        a, b = self.loss.prepare(y_hat, y)
+        if a.shape[0] == 0:
+            return self
+        for r, f in enumerate(self.loss.mel_transfers):
+            f.fold(a, b, self._sum[r:r + 1], self._count[r:r + 1])
+        return self
+
+    def count(self):
+        return [int(c) for c in self._count.cpu()]
+
+    def value(self):
+        s, c = self._sum.cpu().numpy(), self._count.cpu().numpy()
+        if (c == 0).any():
+            return float("nan")
+        return float(np.mean(s / c))
+
+
+def from_config(config, device=None):
+    """The loss a training config enables (codecTrain.py:202-205): MultiMelSpectrogramLoss(**config['mel_loss_params']) when
+    ``use_mel_loss`` is true, else None."""
+    if not config.get("use_mel_loss", False):
+        return None
+    return MultiMelSpectrogramLoss(**config["mel_loss_params"], device=device)

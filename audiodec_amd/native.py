@@ -67,6 +67,10 @@ SYMBOLS = {
     "adk_rvq_lookup": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "adk_rvq_stats_workspace_bytes": (C.c_int64, [_i32, _i32]),
     "adk_rvq_stats": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "adk_mel_workspace_bytes": (C.c_int64, [_i32, _i32, _i32, _i32]),
+    "adk_logmel": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, C.c_float, _vp, _vp]),
+    "adk_mel_distance": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, C.c_float,
+                                   _vp, _vp, _vp, _vp, _vp]),
     "adk_packed_weight_floats_split16": (C.c_int64, [_i32, _i32, _i32]),
     "adk_pack_weights_split16": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "adk_codes_frame_bytes": (C.c_int32, [_i32, _i32]),

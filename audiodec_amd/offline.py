@@ -138,6 +138,14 @@ class TestMain:
         self.encoder_type = self.encoder_config.get("model_type", "symAudioDec")
         self.decoder_type = self.decoder_config.get("model_type", "symAudioDec")
         self.multi_channel = self.encoder_config["generator_params"].get("input_channels", 1) > 1
+        # opt-in (--mel_distance): score every utterance with the encoder config's mel-spectrogram loss (mel.py)
+        self.mel_distance = bool(getattr(args, "mel_distance", False))
+        self.mel_loss = self.mean_mel_distance = None
+        if self.mel_distance:
+            from . import mel
+            self.mel_loss = mel.from_config(self.encoder_config, device=self.device)
+            if self.mel_loss is None:
+                raise ValueError(f"--mel_distance: the encoder config of {args.encoder} enables no mel loss (use_mel_loss)")
 
     def load_dataset(self, subset, subset_num):
         data_path = os.path.join(self.encoder_config["data"]["path"], self.encoder_config["data"]["subset"][subset])
@@ -195,19 +203,36 @@ class TestMain:
     def run(self):
         """bin/test.py:86-104: per-utterance RTF = wall time / audio duration, averaged over utterances."""
         total_rtf, idx = 0.0, 0
+        mel_lines = []
         with torch.no_grad():
             for idx, (utt_id, x) in enumerate(self.dataset, 1):
                 start = time.time()
                 zq = self.encode(x)
-                y = self.decode(zq)
-                y = y.squeeze(1).transpose(1, 0).cpu().numpy()                 # T x C
+                y_dev = self.decode(zq)
+                y = y_dev.squeeze(1).transpose(1, 0).cpu().numpy()             # T x C
                 native.raise_on_device_flags(f"utterance {utt_id}")           # device-side failures -> exceptions
                 rtf = (time.time() - start) / (len(y) / self.decoder_config["sampling_rate"])
                 total_rtf += rtf
+                if self.mel_loss is not None:                                 # outside the RTF timing, before PCM-16
+                    mel_lines.append((utt_id, self.utterance_mel_distance(x, y_dev)))
                 write_wav_pcm16(os.path.join(self.outdir, f"{utt_id}_output.wav"), y, self.decoder_config["sampling_rate"])
         self.mean_rtf = total_rtf / idx
         logging.info("Finished generation of %d utterances (RTF = %.03f)." % (idx, self.mean_rtf))
+        if self.mel_loss is not None:
+            self.mean_mel_distance = float(np.mean([v for _, v in mel_lines]))
+            with open(os.path.join(self.outdir, "mel_distance.txt"), "w") as f:
+                for utt_id, v in mel_lines:
+                    f.write(f"{utt_id} {v:.9g}\n")
+                f.write(f"mean {self.mean_mel_distance:.9g}\n")
+            logging.info("Mel distance of %d utterances: mean %.06f." % (idx, self.mean_mel_distance))
         return self.mean_rtf
+
+    def utterance_mel_distance(self, audio, y):
+        """The encoder config's mel loss between the input audio (T, C) and the float output y (C, 1, T') cropped to the
+        input's length."""
+        x = _streams_of(audio, self.multi_channel).to(self.device)
+        n = min(x.shape[-1], y.shape[-1])
+        return float(self.mel_loss(y[..., :n], x[..., :n]))
 
 
 def _partial_fit(state, X):

@@ -19,6 +19,8 @@ def main():
     parser.add_argument("--decoder", type=str, required=True)
     parser.add_argument("--output_dir", type=str, required=True)
     parser.add_argument("--specific_folder", choices=("True", "False"), default="False")
+    parser.add_argument("--mel_distance", action="store_true",
+                        help="also score each utterance with the encoder config's mel-spectrogram loss (mel_distance.txt)")
     args = parser.parse_args()
 
     test_main = TestMain(args=args)

@@ -222,6 +222,36 @@ int adk_rvq_stats(const float* z, const float* codebook, const int64_t* idx, int
                   float* perplexity, void* stream);
 
 /*
+ * Log-mel spectrogram and mel L1 distance: MelSpectrogram.forward and one resolution of MultiMelSpectrogramLoss.forward
+ * (losses/mel_loss.py:19-156), with torch.stft's defaults as the reference calls it: center=True with reflect padding of n_fft/2
+ * on each side, no normalisation, a one-sided spectrum of n_fft/2 + 1 bins, 1 + n_samples/hop frames.
+ *   x / a / b   [n_signals][n_samples]     signals, contiguous
+ *   window      [win_length]               the analysis window (torch.hann_window(win_length)), centred in n_fft with
+ *                                          (n_fft - win_length)/2 zeros on the left, as torch.stft pads it
+ *   fb_range    [n_mels][3] int32          filter m: first bin, bin count, offset of its weights in fb_weight
+ *   fb_weight   [n_weights]                the nonzero weights of melmat, filter by filter, in bin order
+ *   amp = sqrt(max(re^2 + im^2, eps)); mel = max(sum_k amp[k] w_m[k], eps); log_base 0 = natural log, 2 = log2, 10 = log10.
+ * adk_logmel writes out [n_signals][n_mels][frames] f32.  adk_mel_distance FOLDS sum |logmel(a) - logmel(b)| (f32 difference,
+ * f64 sum) into a caller-owned accumulator on the device (zero it to start; nothing is cleared here):
+ *   sum [1] double += the sum;  count [1] int64 += n_signals * n_mels * frames
+ * and, if loss is not NULL, writes loss [1] f32 = sum / count from the totals after this call's fold (NaN while count == 0).
+ * n_signals == 0 folds nothing.  workspace: adk_mel_workspace_bytes(n_signals, n_samples, n_fft, hop) bytes, 8-byte aligned,
+ * any contents (NULL when that size is 0).  The log-mels are never written to memory; the sum goes through per-workgroup f64
+ * slabs and a fixed-order finalize launch, so it is bitwise reproducible.  Calls on one accumulator must be ordered (one stream).
+ * NaN input gives NaN output, as in the reference.  Limits: n_fft a power of two in [256, 4096], 0 < win_length <= n_fft,
+ * hop > 0, n_samples > n_fft/2 (the reflect padding; torch raises too), 0 < n_mels <= 256, log_base in {0, 2, 10}.  Every
+ * argument is checked before any HIP call (ADK_ERR_ARG).  No allocation, no synchronisation.
+ */
+int64_t adk_mel_workspace_bytes(int32_t n_signals, int32_t n_samples, int32_t n_fft, int32_t hop);
+int adk_logmel(const float* x, int32_t n_signals, int32_t n_samples, int32_t n_fft, int32_t hop, const float* window,
+               int32_t win_length, const int32_t* fb_range, const float* fb_weight, int32_t n_weights, int32_t n_mels,
+               int32_t log_base, float eps, float* out, void* stream);
+int adk_mel_distance(const float* a, const float* b, int32_t n_signals, int32_t n_samples, int32_t n_fft, int32_t hop,
+                     const float* window, int32_t win_length, const int32_t* fb_range, const float* fb_weight, int32_t n_weights,
+                     int32_t n_mels, int32_t log_base, float eps, double* sum, int64_t* count, void* workspace, float* loss,
+                     void* stream);
+
+/*
  * Bit-packed code wire format (the reference passes the int64 index tensor through a
  * queue.Queue, bin/stream.py:224,230, and never serialises it).  One frame of one stream = n_q codes of
  * `bits` bits, LSB-first: code q (= emitted index - size*q) occupies bits [q*bits, (q+1)*bits) of the
