@@ -163,3 +163,30 @@ def synth_audio(seed, stream, length, amp=0.1):
     """x = amp * randn, clipped to [-1, 1] (SURVEY.md section 8d 'synthetic inputs')."""
     x = amp * _randn(seed, ("audio", stream), (length,))
     return np.clip(x, -1.0, 1.0).astype(np.float32)
+
+
+def discriminator_state_dict(params, seed=1337):
+    """Reference-format HiFi-GAN discriminator state dict (models/vocoder/HiFiGAN.py:308-395) for ``discriminator_params``
+    (dict of CPU float32 torch tensors).  Weights are PCG64 output keyed like synth_state_dict's, scaled by He's std for
+    LeakyReLU(0.1), sqrt(2 / 1.01 / fan_in) with fan_in = (C_in / groups) * kernel, so activations stay O(1) through the
+    layers without a calibration pass; biases are 0.1 * randn.  Weight-normed layers store g = ||v|| * u, u in [0.8, 1.25)."""
+    from . import discriminator as D
+    d = D.Discriminator(**dict(params))
+    sd = {}
+    for L in d._layers:
+        if L.norm == "spectral":
+            raise NotImplementedError(f"{L.key}: spectral norm is not implemented on the HIP discriminator")
+        cin_g = L.cin // L.groups
+        shape = (L.cout, cin_g, L.kernel, 1) if L.conv2d else (L.cout, cin_g, L.kernel)
+        std = np.float32(np.sqrt(2.0 / 1.01 / (cin_g * L.kernel)))
+        w = (_randn(seed, ("discriminator", L.key, "w"), shape) * std).astype(np.float32)
+        if L.norm == "weight":
+            norm = np.sqrt((w ** 2).reshape(w.shape[0], -1).sum(1, dtype=np.float32))
+            u = (0.8 + 0.45 * _rng(seed, "discriminator", L.key, "g").random(w.shape[0])).astype(np.float32)
+            sd[f"{L.key}.weight_g"] = torch.from_numpy((norm * u).astype(np.float32).reshape((-1,) + (1,) * (w.ndim - 1)))
+            sd[f"{L.key}.weight_v"] = torch.from_numpy(w)
+        else:
+            sd[f"{L.key}.weight"] = torch.from_numpy(w)
+        if L.bias:
+            sd[f"{L.key}.bias"] = torch.from_numpy(0.1 * _randn(seed, ("discriminator", L.key, "b"), (L.cout,)))
+    return sd

@@ -252,6 +252,34 @@ int adk_mel_distance(const float* a, const float* b, int32_t n_signals, int32_t 
                      void* stream);
 
 /*
+ * HiFi-GAN discriminator forward and its adversarial / feature-matching loss sums (models/vocoder/modules/discriminator.py:27-449,
+ * losses/adversarial_loss.py, losses/feat_match_loss.py), exact f32 (the GEMM runs on the f32-input MFMA: a k-ordered fmaf chain).
+ * adk_disc_conv: a non-causal, zero-padded, strided, grouped conv along H with bias and optional LeakyReLU:
+ *   x [n_items][c_in][h_in][period]  ->  y [n_items][c_out][h_out][period],  h_out = (h_in + 2 pad - kernel) / stride + 1
+ *   y[i][o][h'][j] = act(bias[o] + sum_{ci < c_in/groups, t < kernel} W[o][ci][t] x[i][g c_in/groups + ci][h' stride - pad + t][j])
+ *   with g = o / (c_out/groups), x outside [0, h_in) read as 0, act 0 = none, 2 = LeakyReLU(slope); bias may be NULL.
+ *   impl 1 (direct): w is the reference's layout [c_out][c_in/groups][kernel]; for c_in/groups == 1 or c_out/groups == 1.
+ *   impl 2 (gemm):   w is [groups][c_in/groups * kernel][c_out/groups] (the reference's weight of group g, transposed).
+ *   period = 1 is a Conv1d over (n_items, c_in, h_in); period = p is a (kernel, 1) Conv2d over (n_items, c_in, h_in, p).
+ * adk_disc_prep: op 0 (reflect): y [rows][n_in + a] = x row, continued by reflection at its right end (F.pad 'reflect',
+ *   0 <= a < n_in).  op 1 (avgpool): AvgPool1d(kernel a, stride b, padding c, count_include_pad=True):
+ *   y [rows][(n_in + 2c - a) / b + 1], y[i] = (sum_{q < a} x[i b - c + q], zero outside) / a; 2c <= a.
+ * adk_disc_loss FOLDS the sum over n elements of a term (f32) into a caller-owned f64 accumulator on the device:
+ *   kind 0: (a-1)^2   1: a^2   2: |a - b|   3: a   4: min(a - 1, 0)   5: min(-a - 1, 0)
+ *   sum [1] double += the sum;  count [1] int64 += n;  loss [1] f32 (or NULL) = sum / count after the fold (NaN while count == 0).
+ * workspace: adk_disc_loss_workspace_bytes(n) bytes, 8-byte aligned, any contents (NULL when that size is 0).  Per-workgroup
+ * f64 slabs and a fixed-order finalize launch: bitwise reproducible.  Calls on one accumulator must be ordered (one stream).
+ * Every argument is checked before any HIP call (ADK_ERR_ARG).  No allocation, no synchronisation.
+ */
+int adk_disc_conv(const float* x, const float* w, const float* bias, float* y, int32_t n_items, int32_t c_in, int32_t h_in,
+                  int32_t period, int32_t c_out, int32_t groups, int32_t kernel, int32_t stride, int32_t pad, int32_t act,
+                  float slope, int32_t impl, void* stream);
+int adk_disc_prep(const float* x, float* y, int32_t rows, int32_t n_in, int32_t op, int32_t a, int32_t b, int32_t c, void* stream);
+int64_t adk_disc_loss_workspace_bytes(int64_t n);
+int adk_disc_loss(const float* a, const float* b, int64_t n, int32_t kind, double* sum, int64_t* count, void* workspace,
+                  float* loss, void* stream);
+
+/*
  * Bit-packed code wire format (the reference passes the int64 index tensor through a
  * queue.Queue, bin/stream.py:224,230, and never serialises it).  One frame of one stream = n_q codes of
  * `bits` bits, LSB-first: code q (= emitted index - size*q) occupies bits [q*bits, (q+1)*bits) of the
