@@ -11,10 +11,11 @@
 //   distance mode: |logmel(a) - logmel(b)| in f32, summed per lane in f64, never stored; per-workgroup f64 partials in a slab
 //                  and a fixed-order finalize launch (no float atomics), so the sum is bitwise reproducible run to run.
 #include "adk_common.h"
+#include "fft_wave.h"
 
 namespace adk {
 
-constexpr int MEL_THREADS = 64;                        // one wave per workgroup
+constexpr int MEL_THREADS = FFT_WAVE;                  // one wave per workgroup
 constexpr int MEL_MAX_MELS = 256;
 constexpr int MEL_MPL = MEL_MAX_MELS / 64;             // mel filters per lane
 constexpr int MEL_FB = 16;                             // logmel mode: frames per staged block
@@ -43,16 +44,6 @@ __device__ __forceinline__ float mel_log(float v, int base) {
 // clamp(v, min=eps) as torch.clamp: NaN stays NaN
 __device__ __forceinline__ float clamp_min(float v, float eps) { return v < eps ? eps : v; }
 
-template <int LOG2N>
-__device__ void build_twiddles(float2* tw) {
-    constexpr int NFFT = 2 << LOG2N, N = 1 << LOG2N;
-    for (int k = threadIdx.x; k <= N; k += MEL_THREADS) {
-        double s, c;
-        sincospi(2.0 * (double)k / (double)NFFT, &s, &c);
-        tw[k] = make_float2((float)c, (float)(-s));
-    }
-}
-
 // Log-mels of frame f of signal x into mels[i] = filter lane + 64 i.  buf: n_fft floats of LDS.  Ends with a barrier, so the
 // caller may reuse buf at once.
 template <int LOG2N>
@@ -75,37 +66,16 @@ __device__ void frame_logmel(const float* __restrict__ x, long long f, const Mel
     }
     __syncthreads();
     float2* z = reinterpret_cast<float2*>(buf);
-    // radix-2 DIF: stage with half-span h pairs (i, i + h), twiddle exp(-2 pi i pos / 2h) = tw[pos * N / h]
-#pragma unroll
-    for (int lh = LOG2N - 1; lh >= 0; --lh) {
-        const int h = 1 << lh;
-#pragma unroll 4
-        for (int b = lane; b < N / 2; b += MEL_THREADS) {
-            const int pos = b & (h - 1);
-            const int i = ((b - pos) << 1) + pos;
-            const float2 u = z[i], v = z[i + h];
-            const float2 w = tw[pos << (LOG2N - lh)];
-            const float dx = u.x - v.x, dy = u.y - v.y;
-            z[i] = make_float2(u.x + v.x, u.y + v.y);
-            z[i + h] = make_float2(dx * w.x - dy * w.y, dx * w.y + dy * w.x);
-        }
-        __syncthreads();
-    }
-    // untangle: X[k] = (Z[k] + conj Z[N-k]) / 2 + tw[k] (Z[k] - conj Z[N-k]) / 2i,  Z[k] at bit-reversed address
+    wave_fft_dif<LOG2N>(z, tw);                                  // fft_wave.h: radix-2 DIF, ends with a barrier
+    // untangle through the bit reversal (fft_wave.h)
     float amp[PER];
 #pragma unroll
     for (int q = 0; q < PER; ++q) {
         const int k = lane + q * MEL_THREADS;
         amp[q] = 0.f;
         if (k <= N) {
-            const int k1 = k & (N - 1), k2 = (N - k) & (N - 1);
-            const float2 A = z[__builtin_bitreverse32((unsigned)k1) >> (32 - LOG2N)];
-            const float2 B = z[__builtin_bitreverse32((unsigned)k2) >> (32 - LOG2N)];
-            const float ex = 0.5f * (A.x + B.x), ey = 0.5f * (A.y - B.y);
-            const float ox = 0.5f * (A.y + B.y), oy = -0.5f * (A.x - B.x);
-            const float2 w = tw[k];
-            const float re = ex + (ox * w.x - oy * w.y);
-            const float im = ey + (ox * w.y + oy * w.x);
+            float re, im;
+            wave_fft_bin<LOG2N>(z, tw, k, re, im);
             amp[q] = sqrtf(clamp_min(re * re + im * im, a.eps));
         }
     }

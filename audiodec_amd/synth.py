@@ -165,28 +165,65 @@ def synth_audio(seed, stream, length, amp=0.1):
     return np.clip(x, -1.0, 1.0).astype(np.float32)
 
 
+UNIVNET_ONLY_KEYS = {"fft_sizes", "hop_sizes", "win_lengths", "window", "spectral_discriminator_params", "flat_channel"}
+
+
 def discriminator_state_dict(params, seed=1337):
     """Reference-format HiFi-GAN discriminator state dict (models/vocoder/HiFiGAN.py:308-395) for ``discriminator_params``
     (dict of CPU float32 torch tensors).  Weights are PCG64 output keyed like synth_state_dict's, scaled by He's std for
     LeakyReLU(0.1), sqrt(2 / 1.01 / fan_in) with fan_in = (C_in / groups) * kernel, so activations stay O(1) through the
-    layers without a calibration pass; biases are 0.1 * randn.  Weight-normed layers store g = ||v|| * u, u in [0.8, 1.25)."""
+    layers without a calibration pass; biases are 0.1 * randn.  Weight-normed layers store g = ||v|| * u, u in [0.8, 1.25).
+
+    Parameters that name one of UNIVNET_ONLY_KEYS are UnivNet's and go to univnet_discriminator_state_dict.  The two
+    discriminators share the period arguments, so UnivNet parameters that leave all of those keys to their defaults (only
+    ``periods`` / ``period_discriminator_params``, or {}) cannot be told apart here and are read as HiFi-GAN's: call
+    univnet_discriminator_state_dict directly for them."""
     from . import discriminator as D
+    if UNIVNET_ONLY_KEYS & set(params):
+        return univnet_discriminator_state_dict(params, seed)
     d = D.Discriminator(**dict(params))
+    return _discriminator_layer_tensors(d._layers, seed)
+
+
+def univnet_discriminator_state_dict(params, seed=1337):
+    """Reference-format UnivNet discriminator state dict (models/vocoder/UnivNet.py:23-103) for ``discriminator_params``: the
+    same keying and scaling as discriminator_state_dict (He's std for LeakyReLU(0.2) in the spectral layers, fan_in =
+    C_in * kh * kw), plus every spectral discriminator's ``window`` buffer, torch.hann_window(win_length)."""
+    from . import univnet_discriminator as U
+    d = U.Discriminator(**dict(params))
     sd = {}
-    for L in d._layers:
+    for key, _, _, win in d._specs:
+        sd[key] = torch.hann_window(win)
+    sd.update(_discriminator_layer_tensors(d._layers, seed))
+    return sd
+
+
+def _discriminator_layer_tensors(layers, seed):
+    sd = {}
+    for L in layers:
+        if isinstance(L.kernel, tuple):               # a 2-D spectral layer (univnet_discriminator.SpecLayer)
+            shape, fan_in = (L.cout, L.cin) + L.kernel, L.cin * L.kernel[0] * L.kernel[1]
+            std = np.float32(np.sqrt(2.0 / (1.0 + 0.2 ** 2) / fan_in))
+            w = (_randn(seed, ("discriminator", L.key, "w"), shape) * std).astype(np.float32)
+            _store_layer(sd, L, w, seed)
+            continue
         if L.norm == "spectral":
             raise NotImplementedError(f"{L.key}: spectral norm is not implemented on the HIP discriminator")
         cin_g = L.cin // L.groups
         shape = (L.cout, cin_g, L.kernel, 1) if L.conv2d else (L.cout, cin_g, L.kernel)
         std = np.float32(np.sqrt(2.0 / 1.01 / (cin_g * L.kernel)))
         w = (_randn(seed, ("discriminator", L.key, "w"), shape) * std).astype(np.float32)
-        if L.norm == "weight":
-            norm = np.sqrt((w ** 2).reshape(w.shape[0], -1).sum(1, dtype=np.float32))
-            u = (0.8 + 0.45 * _rng(seed, "discriminator", L.key, "g").random(w.shape[0])).astype(np.float32)
-            sd[f"{L.key}.weight_g"] = torch.from_numpy((norm * u).astype(np.float32).reshape((-1,) + (1,) * (w.ndim - 1)))
-            sd[f"{L.key}.weight_v"] = torch.from_numpy(w)
-        else:
-            sd[f"{L.key}.weight"] = torch.from_numpy(w)
-        if L.bias:
-            sd[f"{L.key}.bias"] = torch.from_numpy(0.1 * _randn(seed, ("discriminator", L.key, "b"), (L.cout,)))
+        _store_layer(sd, L, w, seed)
     return sd
+
+
+def _store_layer(sd, L, w, seed):
+    if L.norm == "weight":
+        norm = np.sqrt((w ** 2).reshape(w.shape[0], -1).sum(1, dtype=np.float32))
+        u = (0.8 + 0.45 * _rng(seed, "discriminator", L.key, "g").random(w.shape[0])).astype(np.float32)
+        sd[f"{L.key}.weight_g"] = torch.from_numpy((norm * u).astype(np.float32).reshape((-1,) + (1,) * (w.ndim - 1)))
+        sd[f"{L.key}.weight_v"] = torch.from_numpy(w)
+    else:
+        sd[f"{L.key}.weight"] = torch.from_numpy(w)
+    if L.bias:
+        sd[f"{L.key}.bias"] = torch.from_numpy(0.1 * _randn(seed, ("discriminator", L.key, "b"), (L.cout,)))

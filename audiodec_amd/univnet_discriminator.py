@@ -1,0 +1,381 @@
+"""UnivNet discriminator on the device: multi-resolution spectral + multi-period (adk_spectrogram, adk_conv2d, adk_disc_*).
+
+Mirrors ``models/vocoder/modules/discriminator.py``: ``UnivNetSpectralDiscriminator`` (lines 451-582) and
+``UnivNetMultiResolutionSpectralDiscriminator`` (lines 585-640), combined with the multi-period discriminator as
+``models/vocoder/UnivNet.py:23-103`` ``Discriminator``, which codecTrain.py builds for the ``symAudioDecUniv`` and ``UnivNet``
+model types.  The period half is ``discriminator.HiFiGANMultiPeriodDiscriminator`` unchanged, and the loss classes,
+``AdversarialEval`` and ``from_config`` of ``discriminator`` work on this module's ``Discriminator`` as they are.
+
+A spectral discriminator is one magnitude spectrogram (``torchaudio.functional.spectrogram`` with ``pad = win_length // 2``,
+``power = 1``, transposed to (frames, bins)) and six 2-D convs over that plane, each one HIP call: an implicit GEMM on the
+f32-input MFMA, or a direct kernel for the C_in = 1 first layer and the C_out = 1 output layer.  Exact f32 throughout.
+
+State dicts use the reference's keys, including the persistent ``window`` buffer of every spectral discriminator; the
+spectrogram uses the loaded window.  Weight norm (``weight_g``/``weight_v``) is folded once at load as
+``torch._weight_norm(v, g, 0)``.
+
+Forward only: an input that requires grad while grad is enabled raises NotImplementedError.
+"""
+import copy
+import os
+from collections import namedtuple
+
+import torch
+
+from . import discriminator as D
+from . import native
+from .discriminator import AdversarialEval, DiscriminatorAdversarialLoss, FeatureMatchLoss, GeneratorAdversarialLoss, from_config  # noqa: F401
+
+ACT_NONE, ACT_LEAKY = D.ACT_NONE, D.ACT_LEAKY
+IMPL_DIRECT, IMPL_GEMM = D.IMPL_DIRECT, D.IMPL_GEMM
+GEMM_MAX_K = 4096                                     # adk_conv2d impl 2: c_in * kh * kw
+
+# one 2-D conv layer: kernel, stride, pad are (frames axis, bins axis); norm "none" | "weight"
+SpecLayer = namedtuple("SpecLayer", "key cin cout kernel stride pad bias act_slope norm")
+
+SPECTRAL_DEFAULTS = dict(kernel_sizes=[(3, 9), (3, 9), (3, 9), (3, 9), (3, 3), (3, 3)],
+                         strides=[(1, 1), (1, 2), (1, 2), (1, 2), (1, 1), (1, 1)], channels=32, bias=True,
+                         nonlinear_activation="LeakyReLU", nonlinear_activation_params={"negative_slope": 0.2},
+                         use_weight_norm=True)
+MRSD_DISC_DEFAULTS = dict(channels=32, kernel_sizes=[(3, 9), (3, 9), (3, 9), (3, 9), (3, 3), (3, 3)],
+                          strides=[(1, 1), (1, 2), (1, 2), (1, 2), (1, 1), (1, 1)], bias=True,
+                          nonlinear_activation="LeakyReLU", nonlinear_activation_params={"negative_slope": 0.2})
+MPD_DISC_DEFAULTS = D.MPD_DISC_DEFAULTS
+
+
+def _pair(v, what):
+    v = (v, v) if isinstance(v, int) else tuple(int(a) for a in v)
+    if len(v) != 2 or min(v) < 1:
+        raise ValueError(f"{what}: expected an int or a pair of positive ints, got {v!r}")
+    return v
+
+
+def spectral_layers(prefix, **kw):
+    """The layers of UnivNetSpectralDiscriminator(**kw) (discriminator.py:490-548), keys under ``prefix``.  NonCausalConv2d
+    pads (k - 1) // 2 on each axis (layers/conv_layer.py:221-224)."""
+    unknown = set(kw) - set(SPECTRAL_DEFAULTS)
+    if unknown:
+        raise TypeError(f"UnivNetSpectralDiscriminator: unexpected arguments {sorted(unknown)}")
+    p = dict(SPECTRAL_DEFAULTS, **kw)
+    if p["nonlinear_activation"] != "LeakyReLU":
+        raise NotImplementedError(f"nonlinear_activation {p['nonlinear_activation']!r}: the HIP discriminator implements LeakyReLU only")
+    slope = float((p["nonlinear_activation_params"] or {}).get("negative_slope", 0.01))
+    ks = [_pair(k, "kernel_sizes") for k in p["kernel_sizes"]]
+    st = [_pair(s, "strides") for s in p["strides"]]
+    assert len(ks) == len(st) and len(ks) >= 3
+    ch, bias, norm = int(p["channels"]), bool(p["bias"]), "weight" if p["use_weight_norm"] else "none"
+    n = len(ks)
+    out = []
+    for i in range(n):
+        last = i == n - 1
+        key = f"{prefix}layers.{i}.conv" if last else f"{prefix}layers.{i}.0.conv"
+        pad = ((ks[i][0] - 1) // 2, (ks[i][1] - 1) // 2)
+        out.append(SpecLayer(key, 1 if i == 0 else ch, 1 if last else ch, ks[i], st[i], pad, bias, None if last else slope, norm))
+    return out
+
+
+def conv2d_out_shape(h, w, layer):
+    return ((h + 2 * layer.pad[0] - layer.kernel[0]) // layer.stride[0] + 1,
+            (w + 2 * layer.pad[1] - layer.kernel[1]) // layer.stride[1] + 1)
+
+
+def spectrogram_shape(t, fft_size, hop_size, win_length):
+    """(frames, bins) of the transposed spectrogram of t samples: pad = win_length // 2 zeros on both sides, centred frames."""
+    return 1 + (t + 2 * (win_length // 2)) // hop_size, fft_size // 2 + 1
+
+
+def min_samples(fft_size, win_length):
+    """The shortest input torch.stft's reflect padding of fft_size // 2 accepts after the zero padding."""
+    return max(1, fft_size // 2 - 2 * (win_length // 2) + 1)
+
+
+def conv_impl(layer):
+    """Kernel per layer: the direct kernel where a GEMM tile would be mostly padding (C_in = 1 or C_out = 1), else the GEMM."""
+    return IMPL_DIRECT if layer.cin == 1 or layer.cout == 1 else IMPL_GEMM
+
+
+def effective_weight(sd, layer):
+    """(C_out, C_in, kh, kw) float32 CPU weight of one spectral layer from a reference state dict (weight norm folded)."""
+    k = layer.key
+    if f"{k}.weight_g" in sd:
+        w = torch._weight_norm(sd[f"{k}.weight_v"].float(), sd[f"{k}.weight_g"].float(), 0)
+    else:
+        w = sd[f"{k}.weight"].float()
+    w = w.detach().cpu()
+    exp = (layer.cout, layer.cin) + tuple(layer.kernel)
+    if tuple(w.shape) != exp:
+        raise ValueError(f"{k}: weight shape {tuple(w.shape)} does not match the configured {exp}")
+    return w.contiguous()
+
+
+def expected_keys(layer):
+    if isinstance(layer, SpecLayer):
+        k = layer.key
+        ks = [f"{k}.weight_g", f"{k}.weight_v"] if layer.norm == "weight" else [f"{k}.weight"]
+        return ks + ([f"{k}.bias"] if layer.bias else [])
+    return D.expected_keys(layer)
+
+
+_ptr = D._ptr
+
+
+class _Conv2d:
+    """One spectral layer's device weights."""
+
+    def __init__(self, layer, w, b, dev):
+        self.layer, self.impl = layer, conv_impl(layer)
+        kg = layer.cin * layer.kernel[0] * layer.kernel[1]
+        if self.impl == IMPL_GEMM:
+            if kg > GEMM_MAX_K:
+                raise NotImplementedError(f"{layer.key}: C_in * kh * kw = {kg} is beyond the HIP 2-D conv's {GEMM_MAX_K}")
+            w = w.reshape(layer.cout, kg).t()                                   # [cin * kh * kw][cout]
+        self.w = w.contiguous().to(dev)
+        self.b = b.float().contiguous().to(dev) if b is not None else None
+
+    def __call__(self, x):
+        """x (N, C_in, H, W) contiguous float32 -> (N, C_out, H', W')."""
+        L = self.layer
+        n, cin, h, w = x.shape
+        ho, wo = conv2d_out_shape(h, w, L)
+        if ho < 1 or wo < 1:
+            raise ValueError(f"{L.key}: input plane {h} x {w} is smaller than the kernel {L.kernel} with padding {L.pad}")
+        y = torch.empty(n, L.cout, ho, wo, dtype=torch.float32, device=x.device)
+        act = ACT_LEAKY if L.act_slope is not None else ACT_NONE
+        native.check(native.lib().adk_conv2d(_ptr(x), _ptr(self.w), _ptr(self.b), _ptr(y), n, cin, h, w, L.cout, L.kernel[0],
+                                             L.kernel[1], L.stride[0], L.stride[1], L.pad[0], L.pad[1], act,
+                                             float(L.act_slope or 0.0), self.impl, native.current_stream(x.device)), "adk_conv2d")
+        return y
+
+
+def spectrogram(x, window, fft_size, hop_size, win_length):
+    """Rows of x (N, T) float32 on the device -> (N, frames, fft_size // 2 + 1): the reference's transposed magnitude
+    spectrogram (discriminator.py:557-566) through adk_spectrogram."""
+    n, t = x.shape
+    _check_length(t, [(None, fft_size, hop_size, win_length)])
+    frames, bins = spectrogram_shape(t, fft_size, hop_size, win_length)
+    out = torch.empty(n, frames, bins, dtype=torch.float32, device=x.device)
+    native.check(native.lib().adk_spectrogram(_ptr(x), n, t, win_length // 2, fft_size, hop_size, _ptr(window), win_length,
+                                              _ptr(out), native.current_stream(x.device)), "adk_spectrogram")
+    return out
+
+
+class _Module(D._Module):
+    """discriminator._Module with 2-D spectral layers and window buffers next to the period discriminator's layers."""
+
+    def _init_spectral(self, specs):
+        self._specs = specs                           # [(window key, fft_size, hop_size, win_length)]
+        self._windows = None
+
+    def state_dict_keys(self):
+        return [s[0] for s in self._specs] + [k for L in self._layers for k in expected_keys(L)]
+
+    def load_state_dict(self, state_dict, strict=True):
+        """Reference keys; weight norm is folded here, once; the window buffers are kept as loaded."""
+        sd = dict(state_dict)
+        for k in sd:
+            if k.endswith(".weight_orig") or k.endswith(".weight_u"):
+                raise NotImplementedError(f"{k}: spectral-norm parameters are not implemented on the HIP discriminator")
+        want = self.state_dict_keys()
+        missing = [k for k in want if k not in sd]
+        wanted = set(want)
+        unexpected = [k for k in sd if k not in wanted]
+        if missing or (strict and unexpected):
+            raise RuntimeError(f"Error(s) in loading state_dict for {type(self).__name__}: missing keys {missing}, "
+                               f"unexpected keys {unexpected}")
+        self._host = [(L, effective_weight(sd, L) if isinstance(L, SpecLayer) else D.effective_weight(sd, L),
+                       sd[f"{L.key}.bias"] if L.bias else None) for L in self._layers]
+        self._host_windows = {}
+        for key, _, _, win in self._specs:
+            w = sd[key].detach().float().cpu().contiguous()
+            if tuple(w.shape) != (win,):
+                raise ValueError(f"{key}: window shape {tuple(w.shape)} does not match win_length {win}")
+            self._host_windows[key] = w
+        self._convs = None
+        self._hand_down()
+        if self._dev is not None:
+            self.to(self._dev)
+        return self
+
+    def to(self, device):
+        dev = torch.device(device)
+        native.require_gpu(dev)
+        if self._dev != dev or self._convs is None:
+            self._dev = dev
+            if getattr(self, "_host", None) is not None:
+                self._convs = {L.key: (_Conv2d if isinstance(L, SpecLayer) else D._Conv)(L, w, b, dev) for L, w, b in self._host}
+                self._windows = {k: w.to(dev) for k, w in self._host_windows.items()}
+        self._share()
+        return self
+
+    def _children(self):
+        return []
+
+    def _hand_down(self):
+        """Sub-discriminators see their own slice of the loaded weights, so each can also be called by itself."""
+        for m in self._children():
+            own = set(m._layers)
+            m._host = [h for h in self._host if h[0] in own]
+            if isinstance(m, _Module):
+                m._host_windows = {s[0]: self._host_windows[s[0]] for s in m._specs}
+                m._hand_down()
+
+    def _share(self):
+        """Sub-discriminators compute with this module's device tensors."""
+        for m in self._children():
+            m._dev, m._convs = self._dev, self._convs
+            if isinstance(m, _Module):
+                m._windows = self._windows
+                m._share()
+
+
+def _check_window(window):
+    if window != "hann_window":
+        raise NotImplementedError(f"window {window!r}: the HIP spectral discriminator implements hann_window only")
+
+
+def _check_length(t, specs):
+    for _, fft, _, win in specs:
+        if t < min_samples(fft, win):
+            raise ValueError(f"input length {t}: the {fft}-point spectrogram's reflect padding of {fft // 2} needs more than "
+                             f"{fft // 2 - 2 * (win // 2)} samples (torch.stft raises for it too)")
+
+
+def _check_fft(fft_size, hop_size, win_length):
+    if fft_size < 256 or fft_size > 4096 or fft_size & (fft_size - 1):
+        raise NotImplementedError(f"fft_size {fft_size}: the HIP spectrogram implements powers of two in [256, 4096]")
+    if not 0 < win_length <= fft_size or hop_size < 1:
+        raise ValueError(f"need 0 < win_length <= fft_size and hop_size > 0, got win_length {win_length}, hop_size {hop_size}")
+
+
+class UnivNetSpectralDiscriminator(_Module):
+    """discriminator.py:451-582 on the HIP path.  Same arguments and defaults."""
+
+    def __init__(self, fft_size, hop_size, win_length, window="hann_window",
+                 kernel_sizes=[(3, 9), (3, 9), (3, 9), (3, 9), (3, 3), (3, 3)],
+                 strides=[(1, 1), (1, 2), (1, 2), (1, 2), (1, 1), (1, 1)], channels=32, bias=True,
+                 nonlinear_activation="LeakyReLU", nonlinear_activation_params={"negative_slope": 0.2}, use_weight_norm=True,
+                 device=None, _prefix=""):
+        _check_window(window)
+        self.fft_size, self.hop_size, self.win_length = int(fft_size), int(hop_size), int(win_length)
+        _check_fft(self.fft_size, self.hop_size, self.win_length)
+        self.window_key = f"{_prefix}window"
+        self.layers = spectral_layers(_prefix, kernel_sizes=kernel_sizes, strides=strides, channels=channels, bias=bias,
+                                      nonlinear_activation=nonlinear_activation,
+                                      nonlinear_activation_params=nonlinear_activation_params, use_weight_norm=use_weight_norm)
+        self.discriminator_layers = [self.layers]
+        self._init_layers(list(self.layers), device)
+        self._init_spectral([(self.window_key, self.fft_size, self.hop_size, self.win_length)])
+
+    def output_shapes(self, n, t):
+        """Shapes of the per-layer outputs for an (n, 1, t) input."""
+        h, w = spectrogram_shape(t, self.fft_size, self.hop_size, self.win_length)
+        out = []
+        for L in self.layers:
+            h, w = conv2d_out_shape(h, w, L)
+            out.append((n, L.cout, h, w))
+        return out
+
+    def layers_of(self, x, d0=0, prepared=False):
+        """Yields (d0, layer, tensor, n_layers) one layer at a time."""
+        if not prepared:
+            x = self._prepare(x)
+            if x.shape[1] != 1:
+                raise ValueError(f"expected a (B, 1, T) input, got {tuple(x.shape)}")
+            _check_length(x.shape[2], self._specs)
+        b, _, t = x.shape
+        h = spectrogram(x.reshape(b, t), self._windows[self.window_key], self.fft_size, self.hop_size, self.win_length)
+        h = h.reshape(b, 1, h.shape[1], h.shape[2])
+        for l, L in enumerate(self.layers):
+            h = self._convs[L.key](h)
+            yield d0, l, h, len(self.layers)
+
+
+class UnivNetMultiResolutionSpectralDiscriminator(_Module):
+    """discriminator.py:585-640 on the HIP path.  Same arguments and defaults."""
+
+    def __init__(self, fft_sizes=[1024, 2048, 512], hop_sizes=[120, 240, 50], win_lengths=[600, 1200, 240], window="hann_window",
+                 discriminator_params=MRSD_DISC_DEFAULTS, device=None, _prefix=""):
+        assert len(fft_sizes) == len(hop_sizes) == len(win_lengths)
+        self.discriminators = []
+        for i in range(len(fft_sizes)):
+            params = copy.deepcopy(dict(discriminator_params))
+            self.discriminators.append(UnivNetSpectralDiscriminator(fft_size=fft_sizes[i], hop_size=hop_sizes[i],
+                                                                    win_length=win_lengths[i], window=window,
+                                                                    _prefix=f"{_prefix}discriminators.{i}.", **params))
+        self.discriminator_layers = [d.layers for d in self.discriminators]
+        self._init_layers([L for ls in self.discriminator_layers for L in ls], device)
+        self._init_spectral([s for d in self.discriminators for s in d._specs])
+
+    def _children(self):
+        return self.discriminators
+
+    def layers_of(self, x, d0=0, prepared=False):
+        if not prepared:
+            x = self._prepare(x)
+            if x.shape[1] != 1:
+                raise ValueError(f"expected a (B, 1, T) input, got {tuple(x.shape)}")
+            _check_length(x.shape[2], self._specs)
+        self._share()
+        for i, d in enumerate(self.discriminators):
+            yield from d.layers_of(x, d0 + i, prepared=True)
+
+
+class Discriminator(_Module):
+    """models/vocoder/UnivNet.py:23-103 on the HIP path: mrsd(x) + mpd(x).  Same arguments and defaults; state-dict keys
+    ``mrsd.…`` (with the ``window`` buffers) and ``mpd.…`` as the reference's."""
+
+    def __init__(self, fft_sizes=[1024, 2048, 512], hop_sizes=[120, 240, 50], win_lengths=[600, 1200, 240], window="hann_window",
+                 spectral_discriminator_params=MRSD_DISC_DEFAULTS, periods=[2, 3, 5, 7, 11],
+                 period_discriminator_params=MPD_DISC_DEFAULTS, flat_channel=False, device=None):
+        self.flat_channel = bool(flat_channel)
+        self.mrsd = UnivNetMultiResolutionSpectralDiscriminator(fft_sizes=fft_sizes, hop_sizes=hop_sizes, win_lengths=win_lengths,
+                                                                window=window, discriminator_params=spectral_discriminator_params,
+                                                                _prefix="mrsd.")
+        self.mpd = D.HiFiGANMultiPeriodDiscriminator(periods=periods, discriminator_params=period_discriminator_params, _prefix="mpd.")
+        self.discriminator_layers = self.mrsd.discriminator_layers + self.mpd.discriminator_layers
+        self._init_layers(self.mrsd._layers + self.mpd._layers, device)
+        self._init_spectral(self.mrsd._specs)
+
+    @property
+    def n_discriminators(self):
+        return len(self.discriminator_layers)
+
+    def _children(self):
+        return [self.mrsd, self.mpd]
+
+    def layers_of(self, x):
+        D._no_grad_inputs(x)
+        if isinstance(x, torch.Tensor) and x.dim() == 3:          # both checks before any launch
+            if x.shape[1] != 1 and not self.flat_channel:
+                raise ValueError(f"input with {x.shape[1]} channels and flat_channel=False: the reference fails inside its first "
+                                 "conv (the spectrogram of a (B, C, T) input has C channels, the conv expects 1); set flat_channel=True")
+            _check_length(x.shape[2], self._specs)
+        x = self._prepare(x)
+        self._share()
+        b, c, t = x.shape
+        if c != 1:
+            x = x.reshape(b * c, 1, t)
+        yield from self.mrsd.layers_of(x, 0, prepared=True)
+        yield from self.mpd.layers_of(x, len(self.mrsd.discriminator_layers), prepared=True)
+
+
+def discriminator_for(model_type, discriminator_params, device=None):
+    """codecTrain.py:140-147: the UnivNet discriminator for symAudioDecUniv / UnivNet, the HiFi-GAN one for symAudioDec / HiFiGAN."""
+    if model_type in ("symAudioDecUniv", "UnivNet"):
+        return Discriminator(**dict(discriminator_params or {}), device=device)
+    return D.discriminator_for(model_type, discriminator_params, device=device)
+
+
+def load_discriminator(checkpoint, device=None):
+    """The discriminator of a training checkpoint of any of the four model types: config.yml next to it,
+    torch.load(checkpoint)['model']['discriminator'] (trainer/trainerGAN.py:95-121).  The returned module's ``config`` is the
+    parsed config.yml."""
+    import yaml
+    cfg_path = os.path.join(os.path.dirname(os.path.abspath(checkpoint)), "config.yml")
+    with open(cfg_path) as f:
+        config = yaml.load(f, Loader=yaml.Loader)
+    disc = discriminator_for(config.get("model_type", "symAudioDec"), config.get("discriminator_params", {}), device=device)
+    state = torch.load(checkpoint, map_location="cpu", weights_only=False)
+    disc.load_state_dict(state["model"]["discriminator"])
+    disc.config = config
+    return disc

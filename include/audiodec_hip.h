@@ -280,6 +280,32 @@ int adk_disc_loss(const float* a, const float* b, int64_t n, int32_t kind, doubl
                   float* loss, void* stream);
 
 /*
+ * UnivNet spectral discriminator forward (models/vocoder/modules/discriminator.py:451-640), exact f32.  The period half of the
+ * UnivNet discriminator is adk_disc_conv / adk_disc_prep, the loss sums are adk_disc_loss.
+ * adk_spectrogram: torchaudio.functional.spectrogram(x, pad, window, n_fft, hop, win_length, power=1.0, normalized=False)
+ *   followed by .transpose(-1, -2): x [n_signals][n_samples] gets `pad` zeros on both sides, then torch.stft's defaults
+ *   (center=True with reflect padding of n_fft/2, the window zero-padded to n_fft centred, one-sided), then |X| with no eps
+ *   clamp.  out [n_signals][frames][n_fft/2 + 1], frames = adk_spectrogram_frames(n_samples, pad, hop) =
+ *   1 + (n_samples + 2 pad) / hop.  Both paddings and the window are applied while loading; there is no padded copy.  The FFT
+ *   is adk_logmel's (one frame per wave, f64 twiddles rounded to f32).  Limits: n_fft a power of two in [256, 4096],
+ *   0 < win_length <= n_fft, hop > 0, pad >= 0, n_samples + 2 pad > n_fft/2 (the reflect padding; torch raises too).
+ * adk_conv2d: x [n_items][c_in][h_in][w_in] -> y [n_items][c_out][h_out][w_out], kernel (kh, kw), stride (sh, sw), zero padding
+ *   (ph, pw), groups = 1, bias [c_out] (may be NULL), act 0 (none) or 2 (LeakyReLU(slope));
+ *   h_out = (h_in + 2 ph - kh) / sh + 1, w_out likewise (ADK_ERR_SHAPE when the kernel is larger than the padded input).
+ *   impl 1 (direct): w is the reference's [c_out][c_in][kh][kw]; for c_in = 1 or c_out = 1.
+ *   impl 2 (gemm):   w is [c_in * kh * kw][c_out] (the reference's weight transposed), c_in * kh * kw <= 4096; an implicit
+ *                    GEMM on the f32-input MFMA.  Both sum in the order kk = (ci*kh + th)*kw + tw, one f32 fmaf chain.
+ * Every argument is checked before any HIP call (ADK_ERR_ARG / ADK_ERR_SHAPE).  No allocation, no synchronisation; results are
+ * bitwise reproducible.
+ */
+int64_t adk_spectrogram_frames(int32_t n_samples, int32_t pad, int32_t hop);
+int adk_spectrogram(const float* x, int32_t n_signals, int32_t n_samples, int32_t pad, int32_t n_fft, int32_t hop,
+                    const float* window, int32_t win_length, float* out, void* stream);
+int adk_conv2d(const float* x, const float* w, const float* bias, float* y, int32_t n_items, int32_t c_in, int32_t h_in,
+               int32_t w_in, int32_t c_out, int32_t kh, int32_t kw, int32_t sh, int32_t sw, int32_t ph, int32_t pw, int32_t act,
+               float slope, int32_t impl, void* stream);
+
+/*
  * Bit-packed code wire format (the reference passes the int64 index tensor through a
  * queue.Queue, bin/stream.py:224,230, and never serialises it).  One frame of one stream = n_q codes of
  * `bits` bits, LSB-first: code q (= emitted index - size*q) occupies bits [q*bits, (q+1)*bits) of the
