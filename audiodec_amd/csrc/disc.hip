@@ -7,31 +7,23 @@
 // there is no transpose and no padded copy: the padding is predicated loads.
 //   GEMM form, per group g:  Y[m][n] = bias[m] + sum_kk W[m][kk] X[kk][n],  m < C_out/g,  kk = ci*k + t < (C_in/g)*k,
 //                            n = (item, h', j) over every output position;  X[kk][n] = x[item][g*C_in/g + ci][h'*s - pad + t][j]
-//   disc_gemm_kernel:   the implicit GEMM on v_mfma_f32_32x32x2_f32 (f32 in, f32 accumulate: a k-ordered fmaf chain, no split
-//                       precision).  Workgroup tile BM x BN x 16 of 4 waves; the 16-deep K slice of W (pre-transposed at load to
-//                       [g][kk][m], coalesced along m) and of the implicit X are staged in LDS, the next slice is loaded into
-//                       registers while the current one is multiplied.  Groups are the grid's z dimension.
+//   disc_gemm_kernel:   that GEMM through conv_gemm_f32.h's core (W pre-transposed at load to [g][kk][m]); DiscSrc is the
+//                       addressing above.  Groups are the grid's z dimension.
 //   disc_direct_kernel: one thread per output (or 8 threads splitting C_in/g, summed in a fixed order), for the C_in = 1 first
 //                       layers and the C_out = 1 output layers, where a GEMM tile would be mostly padding.
 //   disc_prep_kernel:   right-side reflect padding (the period discriminator's F.pad(x, (0, n_pad), "reflect")) and
 //                       AvgPool1d with count_include_pad (the scale discriminator's pooling between scales).
 //   disc_loss_kernel:   sum over a tensor of (x-1)^2, x^2, |a-b|, x, min(x-1, 0) or min(-x-1, 0) (f32 term, f64 sum) through
 //                       per-workgroup f64 partials and a fixed-order finalize launch: bitwise reproducible run to run.
-#include "adk_common.h"
+#include "conv_gemm_f32.h"
 
 namespace adk {
 
-constexpr int DISC_THREADS = 256;
-constexpr int DISC_KT = 16;                         // K depth of one LDS slice
-constexpr int DISC_ACT_NONE = 0, DISC_ACT_LEAKY = 2;
-constexpr int DISC_IMPL_DIRECT = 1, DISC_IMPL_GEMM = 2;
 constexpr int DISC_PREP_REFLECT = 0, DISC_PREP_AVGPOOL = 1;
 constexpr int DISC_LOSS_MSE_ONE = 0, DISC_LOSS_SQ = 1, DISC_LOSS_L1 = 2, DISC_LOSS_SUM = 3, DISC_LOSS_HINGE_REAL = 4,
               DISC_LOSS_HINGE_FAKE = 5;
 constexpr int DISC_LOSS_MAX_WG = 1024;
 constexpr int DISC_DIRECT_SPLIT = 8;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct DiscConv {
     const float* x;
@@ -45,124 +37,47 @@ struct DiscConv {
     long long n_cols;                               // n_items * hp_out: GEMM N
 };
 
-__device__ __forceinline__ float disc_act(float v, const DiscConv& c) {
-    return (c.act == DISC_ACT_LEAKY && v < 0.f) ? v * c.slope : v;
-}
-
-// Implicit GEMM: workgroup tile BM x BN, WM x WN waves each holding TM x TN tiles of 32 x 32.
-template <int WM, int WN, int TM, int TN>
-__global__ __launch_bounds__(DISC_THREADS) void disc_gemm_kernel(DiscConv c) {
-    static_assert(WM * WN * 64 == DISC_THREADS, "four waves");
-    constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
-    static_assert(DISC_THREADS % BN == 0 && (BM * DISC_KT) % DISC_THREADS == 0, "tile shape");
-    constexpr int LDA = (BM % 64 == 0) ? BM + 32 : BM;        // lanes 32..63 read the next K row: put it 32 banks over
-    constexpr int LDB = (BN % 64 == 0) ? BN + 32 : BN;
-    constexpr int A_PER = BM * DISC_KT / DISC_THREADS;
-    constexpr int B_PER = BN * DISC_KT / DISC_THREADS;
-    constexpr int B_KSTEP = DISC_THREADS / BN;
-    __shared__ float As[DISC_KT * LDA];
-    __shared__ float Bs[DISC_KT * LDB];
-
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int wm = wid / WN, wn = wid % WN;
+// What conv_gemm_f32 needs of a DiscConv: group g = blockIdx.z; tap kk = ci*k + t of a column is a division along H.
+struct DiscSrc {
+    const DiscConv& c;
     const int g = blockIdx.z;
-    const int m0 = blockIdx.y * BM;
-    const long long n0 = (long long)blockIdx.x * BN;
-
-    // this thread's implicit-X column (fixed over the K loop)
-    const int bn = tid % BN, bk0 = tid / BN;
-    const long long col = n0 + bn;
-    const bool col_ok = col < c.n_cols;
     long long xbase = 0;
-    int hb = 0;
-    if (col_ok) {
-        const long long item = col / c.hp_out;
-        const long long rem = col - item * c.hp_out;
-        const int ho = (int)(rem / c.period), j = (int)(rem - (long long)ho * c.period);
-        xbase = ((item * c.c_in + (long long)g * c.cin_g) * c.h_in) * c.period + j;
-        hb = ho * c.stride - c.pad;
+    int hb = -0x40000000;                           // an invalid column fails the bounds test
+    __device__ int k_extent() const { return c.kg; }
+    __device__ int m_extent() const { return c.cout_g; }
+    __device__ long long n_cols() const { return c.n_cols; }
+    __device__ const float* weights() const { return c.w + (size_t)g * c.kg * c.cout_g; }
+    __device__ void column(long long col) {
+        if (col < c.n_cols) {
+            const long long item = col / c.hp_out;
+            const long long rem = col - item * c.hp_out;
+            const int ho = (int)(rem / c.period), j = (int)(rem - (long long)ho * c.period);
+            xbase = ((item * c.c_in + (long long)g * c.cin_g) * c.h_in) * c.period + j;
+            hb = ho * c.stride - c.pad;
+        }
     }
-    const float* __restrict__ wg = c.w + (size_t)g * c.kg * c.cout_g;
-
-    float ra[A_PER], rb[B_PER];
-    auto load = [&](int k0) {
-#pragma unroll
-        for (int i = 0; i < A_PER; ++i) {
-            const int e = tid + i * DISC_THREADS;
-            const int k = k0 + e / BM, m = m0 + e % BM;
-            ra[i] = (k < c.kg && m < c.cout_g) ? wg[(size_t)k * c.cout_g + m] : 0.f;
-        }
-#pragma unroll
-        for (int i = 0; i < B_PER; ++i) {
-            const int kk = k0 + bk0 + i * B_KSTEP;
-            const int ci = kk / c.ksz, h = hb + (kk - ci * c.ksz);
-            const bool ok = col_ok && kk < c.kg && (unsigned)h < (unsigned)c.h_in;
-            rb[i] = ok ? c.x[xbase + ((long long)ci * c.h_in + h) * c.period] : 0.f;
-        }
-    };
-    auto store = [&]() {
-#pragma unroll
-        for (int i = 0; i < A_PER; ++i) {
-            const int e = tid + i * DISC_THREADS;
-            As[(e / BM) * LDA + e % BM] = ra[i];
-        }
-#pragma unroll
-        for (int i = 0; i < B_PER; ++i) Bs[(bk0 + i * B_KSTEP) * LDB + bn] = rb[i];
-    };
-
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int a = 0; a < TM; ++a)
-#pragma unroll
-        for (int b = 0; b < TN; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-
-    const int n_kt = (c.kg + DISC_KT - 1) / DISC_KT;
-    load(0);
-    const int arow = wm * TM * 32 + (lane & 31), brow = wn * TN * 32 + (lane & 31), kh = lane >> 5;
-    for (int kt = 0; kt < n_kt; ++kt) {
-        store();
-        __syncthreads();
-        if (kt + 1 < n_kt) load((kt + 1) * DISC_KT);
-#pragma unroll
-        for (int kk = 0; kk < DISC_KT; kk += 2) {
-            float av[TM], bv[TN];
-#pragma unroll
-            for (int a = 0; a < TM; ++a) av[a] = As[(kk + kh) * LDA + arow + a * 32];
-#pragma unroll
-            for (int b = 0; b < TN; ++b) bv[b] = Bs[(kk + kh) * LDB + brow + b * 32];
-#pragma unroll
-            for (int a = 0; a < TM; ++a)
-#pragma unroll
-                for (int b = 0; b < TN; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[a], bv[b], acc[a][b], 0, 0, 0);
-        }
-        __syncthreads();
+    __device__ float tap(int kk) const {
+        const int ci = kk / c.ksz, h = hb + (kk - ci * c.ksz);
+        const bool ok = kk < c.kg && (unsigned)h < (unsigned)c.h_in;
+        return ok ? c.x[xbase + ((long long)ci * c.h_in + h) * c.period] : 0.f;
     }
-
-    // epilogue: C/D map col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
-#pragma unroll
-    for (int b = 0; b < TN; ++b) {
-        const long long n = n0 + wn * TN * 32 + b * 32 + (lane & 31);
-        if (n >= c.n_cols) continue;
+    __device__ float* out(long long n) const {
         const long long item = n / c.hp_out, rem = n - item * c.hp_out;
-        float* yb = c.y + (item * c.c_out + (long long)g * c.cout_g) * c.hp_out + rem;
-#pragma unroll
-        for (int a = 0; a < TM; ++a)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm * TM * 32 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                if (m < c.cout_g) {
-                    const float bias = c.bias ? c.bias[g * c.cout_g + m] : 0.f;
-                    yb[(long long)m * c.hp_out] = disc_act(acc[a][b][r] + bias, c);
-                }
-            }
+        return c.y + (item * c.c_out + (long long)g * c.cout_g) * c.hp_out + rem;
     }
+    __device__ long long out_stride() const { return c.hp_out; }
+    __device__ int bias_index(int m) const { return g * c.cout_g + m; }
+};
+
+template <int WM, int WN, int TM, int TN>
+__global__ __launch_bounds__(CG_THREADS) void disc_gemm_kernel(DiscConv c) {
+    DiscSrc src{c};
+    conv_gemm_f32<WM, WN, TM, TN>(src, c.bias, c.act, c.slope);
 }
 
 // One output per x-thread; blockDim.y threads split the group's input channels and are summed in y order.
-__global__ __launch_bounds__(DISC_THREADS) void disc_direct_kernel(DiscConv c) {
-    __shared__ float part[DISC_THREADS];
+__global__ __launch_bounds__(CG_THREADS) void disc_direct_kernel(DiscConv c) {
+    __shared__ float part[CG_THREADS];
     const int split = blockDim.y;
     const long long o = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const long long total = c.n_cols * c.c_out;
@@ -197,16 +112,16 @@ __global__ __launch_bounds__(DISC_THREADS) void disc_direct_kernel(DiscConv c) {
     }
     if (o < total) {
         const float bias = c.bias ? c.bias[co] : 0.f;
-        c.y[(item * c.c_out + co) * c.hp_out + rem] = disc_act(s + bias, c);
+        c.y[(item * c.c_out + co) * c.hp_out + rem] = cg_act(s + bias, c.act, c.slope);
     }
 }
 
 // op REFLECT: y [rows][n_in + a] = x, then x[2 (n_in - 1) - t] for t >= n_in  (a < n_in).
 // op AVGPOOL: y [rows][(n_in + 2c - a) / b + 1],  y[i] = sum_{q < a} x[i b - c + q] (zero outside) / a.
-__global__ __launch_bounds__(DISC_THREADS) void disc_prep_kernel(const float* __restrict__ x, float* __restrict__ y, int rows, int n_in,
-                                                                 int n_out, int op, int a, int b, int c) {
+__global__ __launch_bounds__(CG_THREADS) void disc_prep_kernel(const float* __restrict__ x, float* __restrict__ y, int rows, int n_in,
+                                                               int n_out, int op, int a, int b, int c) {
     const long long total = (long long)rows * n_out;
-    for (long long o = (long long)blockIdx.x * DISC_THREADS + threadIdx.x; o < total; o += (long long)gridDim.x * DISC_THREADS) {
+    for (long long o = (long long)blockIdx.x * CG_THREADS + threadIdx.x; o < total; o += (long long)gridDim.x * CG_THREADS) {
         const long long r = o / n_out;
         const int i = (int)(o - r * n_out);
         const float* xr = x + r * n_in;
@@ -227,7 +142,7 @@ __global__ __launch_bounds__(DISC_THREADS) void disc_prep_kernel(const float* __
 }
 
 static int disc_loss_workgroups(long long n) {
-    return (int)std::min<long long>(std::max<long long>((n + 4LL * DISC_THREADS - 1) / (4LL * DISC_THREADS), 1), DISC_LOSS_MAX_WG);
+    return (int)std::min<long long>(std::max<long long>((n + 4LL * CG_THREADS - 1) / (4LL * CG_THREADS), 1), DISC_LOSS_MAX_WG);
 }
 
 template <int KIND>
@@ -242,11 +157,11 @@ __device__ __forceinline__ double disc_term(const float* __restrict__ a, const f
 }
 
 template <int KIND>
-__global__ __launch_bounds__(DISC_THREADS) void disc_loss_kernel(const float* __restrict__ a, const float* __restrict__ b, long long n,
-                                                                 double* __restrict__ partial) {
-    __shared__ double wsum[DISC_THREADS / 64];
+__global__ __launch_bounds__(CG_THREADS) void disc_loss_kernel(const float* __restrict__ a, const float* __restrict__ b, long long n,
+                                                               double* __restrict__ partial) {
+    __shared__ double wsum[CG_THREADS / 64];
     double acc = 0.0;
-    for (long long i = (long long)blockIdx.x * DISC_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * DISC_THREADS)
+    for (long long i = (long long)blockIdx.x * CG_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * CG_THREADS)
         acc += disc_term<KIND>(a, b, i);
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
@@ -254,7 +169,7 @@ __global__ __launch_bounds__(DISC_THREADS) void disc_loss_kernel(const float* __
     __syncthreads();
     if (threadIdx.x == 0) {
         double t = wsum[0];
-        for (int w = 1; w < DISC_THREADS / 64; ++w) t += wsum[w];
+        for (int w = 1; w < CG_THREADS / 64; ++w) t += wsum[w];
         partial[blockIdx.x] = t;
     }
 }
@@ -281,7 +196,7 @@ template <int WM, int WN, int TM, int TN>
 static void launch_gemm(const DiscConv& c, hipStream_t s) {
     constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
     const dim3 grid((unsigned)((c.n_cols + BN - 1) / BN), (unsigned)((c.cout_g + BM - 1) / BM), (unsigned)c.groups);
-    hipLaunchKernelGGL((disc_gemm_kernel<WM, WN, TM, TN>), grid, dim3(DISC_THREADS), 0, s, c);
+    hipLaunchKernelGGL((disc_gemm_kernel<WM, WN, TM, TN>), grid, dim3(CG_THREADS), 0, s, c);
 }
 
 }  // namespace adk
@@ -294,8 +209,8 @@ extern "C" int adk_disc_conv(const float* x, const float* w, const float* bias, 
     if (n_items < 0 || c_in <= 0 || h_in <= 0 || period <= 0 || c_out <= 0 || groups <= 0 || kernel <= 0 || stride <= 0 || pad < 0)
         return fail(ADK_ERR_ARG, "adk_disc_conv: need n_items >= 0, c_in, h_in, period, c_out, groups, kernel, stride > 0, pad >= 0");
     if (c_in % groups || c_out % groups) return fail(ADK_ERR_ARG, "adk_disc_conv: groups must divide c_in and c_out");
-    if (act != DISC_ACT_NONE && act != DISC_ACT_LEAKY) return fail(ADK_ERR_ARG, "adk_disc_conv: act must be 0 (none) or 2 (leaky)");
-    if (impl != DISC_IMPL_DIRECT && impl != DISC_IMPL_GEMM) return fail(ADK_ERR_ARG, "adk_disc_conv: impl must be 1 (direct) or 2 (gemm)");
+    if (act != CG_ACT_NONE && act != CG_ACT_LEAKY) return fail(ADK_ERR_ARG, "adk_disc_conv: act must be 0 (none) or 2 (leaky)");
+    if (impl != CG_IMPL_DIRECT && impl != CG_IMPL_GEMM) return fail(ADK_ERR_ARG, "adk_disc_conv: impl must be 1 (direct) or 2 (gemm)");
     const long long span = (long long)h_in + 2LL * pad - kernel;
     if (span < 0) return fail(ADK_ERR_ARG, "adk_disc_conv: kernel longer than the padded input");
     const long long h_out = span / stride + 1;
@@ -315,9 +230,9 @@ extern "C" int adk_disc_conv(const float* x, const float* w, const float* bias, 
     c.n_cols = (long long)n_items * c.hp_out;
     hipStream_t s = static_cast<hipStream_t>(stream);
     DeviceGuard guard(device_of(y));
-    if (impl == DISC_IMPL_DIRECT) {
+    if (impl == CG_IMPL_DIRECT) {
         const int split = c.cin_g >= 64 ? DISC_DIRECT_SPLIT : 1;
-        const int bx = DISC_THREADS / split;
+        const int bx = CG_THREADS / split;
         const long long total = c.n_cols * c_out;
         const long long nb = (total + bx - 1) / bx;
         if (nb >= (1LL << 31)) return fail(ADK_ERR_ARG, "adk_disc_conv: layer too large for the direct kernel");
@@ -355,8 +270,8 @@ extern "C" int adk_disc_prep(const float* x, float* y, int32_t rows, int32_t n_i
     hipStream_t s = static_cast<hipStream_t>(stream);
     DeviceGuard guard(device_of(y));
     const long long total = (long long)rows * n_out;
-    const int nb = (int)std::min<long long>((total + DISC_THREADS - 1) / DISC_THREADS, 8192);
-    hipLaunchKernelGGL(disc_prep_kernel, dim3(nb), dim3(DISC_THREADS), 0, s, x, y, rows, n_in, (int)n_out, op, a, b, c);
+    const int nb = (int)std::min<long long>((total + CG_THREADS - 1) / CG_THREADS, 8192);
+    hipLaunchKernelGGL(disc_prep_kernel, dim3(nb), dim3(CG_THREADS), 0, s, x, y, rows, n_in, (int)n_out, op, a, b, c);
     ADK_HIP_CHECK(hipGetLastError());
     return ADK_OK;
 }
@@ -384,12 +299,12 @@ extern "C" int adk_disc_loss(const float* a, const float* b, int64_t n, int32_t 
     double* partial = static_cast<double*>(workspace);
     if (n > 0) {
         switch (kind) {
-            case DISC_LOSS_MSE_ONE: hipLaunchKernelGGL(disc_loss_kernel<DISC_LOSS_MSE_ONE>, dim3(n_wg), dim3(DISC_THREADS), 0, s, a, b, n, partial); break;
-            case DISC_LOSS_SQ: hipLaunchKernelGGL(disc_loss_kernel<DISC_LOSS_SQ>, dim3(n_wg), dim3(DISC_THREADS), 0, s, a, b, n, partial); break;
-            case DISC_LOSS_L1: hipLaunchKernelGGL(disc_loss_kernel<DISC_LOSS_L1>, dim3(n_wg), dim3(DISC_THREADS), 0, s, a, b, n, partial); break;
-            case DISC_LOSS_SUM: hipLaunchKernelGGL(disc_loss_kernel<DISC_LOSS_SUM>, dim3(n_wg), dim3(DISC_THREADS), 0, s, a, b, n, partial); break;
-            case DISC_LOSS_HINGE_REAL: hipLaunchKernelGGL(disc_loss_kernel<DISC_LOSS_HINGE_REAL>, dim3(n_wg), dim3(DISC_THREADS), 0, s, a, b, n, partial); break;
-            default: hipLaunchKernelGGL(disc_loss_kernel<DISC_LOSS_HINGE_FAKE>, dim3(n_wg), dim3(DISC_THREADS), 0, s, a, b, n, partial); break;
+            case DISC_LOSS_MSE_ONE: hipLaunchKernelGGL(disc_loss_kernel<DISC_LOSS_MSE_ONE>, dim3(n_wg), dim3(CG_THREADS), 0, s, a, b, n, partial); break;
+            case DISC_LOSS_SQ: hipLaunchKernelGGL(disc_loss_kernel<DISC_LOSS_SQ>, dim3(n_wg), dim3(CG_THREADS), 0, s, a, b, n, partial); break;
+            case DISC_LOSS_L1: hipLaunchKernelGGL(disc_loss_kernel<DISC_LOSS_L1>, dim3(n_wg), dim3(CG_THREADS), 0, s, a, b, n, partial); break;
+            case DISC_LOSS_SUM: hipLaunchKernelGGL(disc_loss_kernel<DISC_LOSS_SUM>, dim3(n_wg), dim3(CG_THREADS), 0, s, a, b, n, partial); break;
+            case DISC_LOSS_HINGE_REAL: hipLaunchKernelGGL(disc_loss_kernel<DISC_LOSS_HINGE_REAL>, dim3(n_wg), dim3(CG_THREADS), 0, s, a, b, n, partial); break;
+            default: hipLaunchKernelGGL(disc_loss_kernel<DISC_LOSS_HINGE_FAKE>, dim3(n_wg), dim3(CG_THREADS), 0, s, a, b, n, partial); break;
         }
         ADK_HIP_CHECK(hipGetLastError());
     }

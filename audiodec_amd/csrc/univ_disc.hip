@@ -8,27 +8,19 @@
 //                        while loading); out [s][f][k] = |X_f[k]|, k <= n_fft/2, no eps clamp.  One frame per wave, the FFT of
 //                        fft_wave.h (shared with mel.hip); a frame's bins are one coalesced run of the output.
 //   conv2d_gemm_kernel:  x [n][c_in][H][W] -> y [n][c_out][H'][W'], kernel (kh, kw), stride (sh, sw), zero padding (ph, pw) by
-//                        predicated loads, as an implicit GEMM on v_mfma_f32_32x32x2_f32 (a k-ordered fmaf chain):
+//                        predicated loads, as an implicit GEMM through conv_gemm_f32.h's core:
 //                          Y[m][n] = bias[m] + sum_kk W[kk][m] X[kk][n],  m < c_out,  kk = (ci*kh + th)*kw + tw,
 //                          n = (item, h', w');  X[kk][n] = x[item][ci][h'*sh - ph + th][w'*sw - pw + tw]
-//                        Tiling and LDS staging as disc_gemm_kernel.  What differs is the implicit-X address: both axes have
-//                        taps and strides, so kk -> (input offset, th, tw) comes from a table built once per workgroup in LDS
-//                        (no division in the K loop), and a thread's fixed column gives (item base, h0, w0).
+//                        Conv2dSrc is that addressing; the wrapper builds its kk table once per workgroup in LDS.
 //   conv2d_direct_kernel: one thread per output position and block of COB output channels, for the c_in = 1 first layer and
 //                        the c_out = 1 output layer, where a GEMM tile would be mostly padding.  Same k order.
-#include "adk_common.h"
+#include "conv_gemm_f32.h"
 #include "fft_wave.h"
 
 namespace adk {
 
-constexpr int UD_THREADS = 256;
-constexpr int UD_KT = 16;                           // K depth of one LDS slice
-constexpr int UD_ACT_NONE = 0, UD_ACT_LEAKY = 2;
-constexpr int UD_IMPL_DIRECT = 1, UD_IMPL_GEMM = 2;
 constexpr int UD_MAX_K = 4096;                      // GEMM: rows of the kk table (8 bytes each in LDS)
 constexpr int UD_SPEC_MAX_WG = 8192;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // ---- magnitude spectrogram ----
 struct SpecArgs {
@@ -95,33 +87,47 @@ struct Conv2dArgs {
     long long n_cols;                               // n_items * hw_out: GEMM N
 };
 
-__device__ __forceinline__ float ud_act(float v, const Conv2dArgs& c) {
-    return (c.act == UD_ACT_LEAKY && v < 0.f) ? v * c.slope : v;
-}
+// What conv_gemm_f32 needs of a Conv2dArgs: both axes have taps and strides, so kk -> (input offset, th, tw) comes from ktab,
+// a table in dynamic LDS (no division in the K loop), and a column gives (item base, h0, w0).
+struct Conv2dSrc {
+    const Conv2dArgs& c;
+    const int2* ktab;                               // [kg rounded up to CG_KT]: .x input offset of tap kk, .y th | tw << 16
+    long long xbase = 0;
+    int h0 = -0x40000000, w0 = -0x40000000;         // an invalid column fails every bounds test
+    __device__ int k_extent() const { return c.kg; }
+    __device__ int m_extent() const { return c.c_out; }
+    __device__ long long n_cols() const { return c.n_cols; }
+    __device__ const float* weights() const { return c.w; }
+    __device__ void column(long long col) {
+        if (col < c.n_cols) {
+            const long long item = col / c.hw_out;
+            const long long rem = col - item * c.hw_out;
+            const int ho = (int)(rem / c.w_out), wo = (int)(rem - (long long)ho * c.w_out);
+            h0 = ho * c.sh - c.ph;
+            w0 = wo * c.sw - c.pw;
+            xbase = item * c.c_in * c.hw_in + (long long)h0 * c.w_in + w0;
+        }
+    }
+    __device__ float tap(int kk) const {
+        const int2 e = ktab[kk];
+        const int h = h0 + (e.y & 0xffff), w = w0 + (e.y >> 16);
+        const bool ok = e.y >= 0 && (unsigned)h < (unsigned)c.h_in && (unsigned)w < (unsigned)c.w_in;
+        return ok ? c.x[xbase + e.x] : 0.f;
+    }
+    __device__ float* out(long long n) const {
+        const long long item = n / c.hw_out, rem = n - item * c.hw_out;
+        return c.y + item * c.c_out * c.hw_out + rem;
+    }
+    __device__ long long out_stride() const { return c.hw_out; }
+    __device__ int bias_index(int m) const { return m; }
+};
 
-// Implicit GEMM: workgroup tile BM x BN, WM x WN waves each holding TM x TN tiles of 32 x 32.  Dynamic LDS: the kk table.
 template <int WM, int WN, int TM, int TN>
-__global__ __launch_bounds__(UD_THREADS) void conv2d_gemm_kernel(Conv2dArgs c) {
-    static_assert(WM * WN * 64 == UD_THREADS, "four waves");
-    constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
-    static_assert(UD_THREADS % BN == 0 && (BM * UD_KT) % UD_THREADS == 0, "tile shape");
-    constexpr int LDA = (BM % 64 == 0) ? BM + 32 : BM;        // lanes 32..63 read the next K row: put it 32 banks over
-    constexpr int LDB = (BN % 64 == 0) ? BN + 32 : BN;
-    constexpr int A_PER = BM * UD_KT / UD_THREADS;
-    constexpr int B_PER = BN * UD_KT / UD_THREADS;
-    constexpr int B_KSTEP = UD_THREADS / BN;
-    __shared__ float As[UD_KT * LDA];
-    __shared__ float Bs[UD_KT * LDB];
-    extern __shared__ int2 ktab[];                  // [kg rounded up to UD_KT]: .x input offset of tap kk, .y th | tw << 16
-
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int wm = wid / WN, wn = wid % WN;
-    const int m0 = blockIdx.y * BM;
-    const long long n0 = (long long)blockIdx.x * BN;
-
-    const int n_kt = (c.kg + UD_KT - 1) / UD_KT;
+__global__ __launch_bounds__(CG_THREADS) void conv2d_gemm_kernel(Conv2dArgs c) {
+    extern __shared__ int2 ktab[];
+    const int n_kt = (c.kg + CG_KT - 1) / CG_KT;
     const int khw = c.kh * c.kw;
-    for (int kk = tid; kk < n_kt * UD_KT; kk += UD_THREADS) {
+    for (int kk = threadIdx.x; kk < n_kt * CG_KT; kk += CG_THREADS) {
         int2 e = make_int2(0, -1);                             // past K: never loaded
         if (kk < c.kg) {
             const int ci = kk / khw, r = kk - ci * khw;
@@ -130,102 +136,15 @@ __global__ __launch_bounds__(UD_THREADS) void conv2d_gemm_kernel(Conv2dArgs c) {
         }
         ktab[kk] = e;
     }
-
-    // this thread's implicit-X column (fixed over the K loop)
-    const int bn = tid % BN, bk0 = tid / BN;
-    const long long col = n0 + bn;
-    const bool col_ok = col < c.n_cols;
-    long long xbase = 0;
-    int h0 = -0x40000000, w0 = -0x40000000;                   // an invalid column fails every bounds test
-    if (col_ok) {
-        const long long item = col / c.hw_out;
-        const long long rem = col - item * c.hw_out;
-        const int ho = (int)(rem / c.w_out), wo = (int)(rem - (long long)ho * c.w_out);
-        h0 = ho * c.sh - c.ph;
-        w0 = wo * c.sw - c.pw;
-        xbase = item * c.c_in * c.hw_in + (long long)h0 * c.w_in + w0;
-    }
     __syncthreads();
-
-    float ra[A_PER], rb[B_PER];
-    auto load = [&](int k0) {
-#pragma unroll
-        for (int i = 0; i < A_PER; ++i) {
-            const int e = tid + i * UD_THREADS;
-            const int k = k0 + e / BM, m = m0 + e % BM;
-            ra[i] = (k < c.kg && m < c.c_out) ? c.w[(size_t)k * c.c_out + m] : 0.f;
-        }
-#pragma unroll
-        for (int i = 0; i < B_PER; ++i) {
-            const int2 e = ktab[k0 + bk0 + i * B_KSTEP];
-            const int h = h0 + (e.y & 0xffff), w = w0 + (e.y >> 16);
-            const bool ok = e.y >= 0 && (unsigned)h < (unsigned)c.h_in && (unsigned)w < (unsigned)c.w_in;
-            rb[i] = ok ? c.x[xbase + e.x] : 0.f;
-        }
-    };
-    auto store = [&]() {
-#pragma unroll
-        for (int i = 0; i < A_PER; ++i) {
-            const int e = tid + i * UD_THREADS;
-            As[(e / BM) * LDA + e % BM] = ra[i];
-        }
-#pragma unroll
-        for (int i = 0; i < B_PER; ++i) Bs[(bk0 + i * B_KSTEP) * LDB + bn] = rb[i];
-    };
-
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int a = 0; a < TM; ++a)
-#pragma unroll
-        for (int b = 0; b < TN; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-
-    load(0);
-    const int arow = wm * TM * 32 + (lane & 31), brow = wn * TN * 32 + (lane & 31), khalf = lane >> 5;
-    for (int kt = 0; kt < n_kt; ++kt) {
-        store();
-        __syncthreads();
-        if (kt + 1 < n_kt) load((kt + 1) * UD_KT);
-#pragma unroll
-        for (int kk = 0; kk < UD_KT; kk += 2) {
-            float av[TM], bv[TN];
-#pragma unroll
-            for (int a = 0; a < TM; ++a) av[a] = As[(kk + khalf) * LDA + arow + a * 32];
-#pragma unroll
-            for (int b = 0; b < TN; ++b) bv[b] = Bs[(kk + khalf) * LDB + brow + b * 32];
-#pragma unroll
-            for (int a = 0; a < TM; ++a)
-#pragma unroll
-                for (int b = 0; b < TN; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[a], bv[b], acc[a][b], 0, 0, 0);
-        }
-        __syncthreads();
-    }
-
-    // epilogue: C/D map col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
-#pragma unroll
-    for (int b = 0; b < TN; ++b) {
-        const long long n = n0 + wn * TN * 32 + b * 32 + (lane & 31);
-        if (n >= c.n_cols) continue;
-        const long long item = n / c.hw_out, rem = n - item * c.hw_out;
-        float* yb = c.y + item * c.c_out * c.hw_out + rem;
-#pragma unroll
-        for (int a = 0; a < TM; ++a)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm * TM * 32 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                if (m < c.c_out) {
-                    const float bias = c.bias ? c.bias[m] : 0.f;
-                    yb[(long long)m * c.hw_out] = ud_act(acc[a][b][r] + bias, c);
-                }
-            }
-    }
+    Conv2dSrc src{c, ktab};
+    conv_gemm_f32<WM, WN, TM, TN>(src, c.bias, c.act, c.slope);
 }
 
 // One thread per (item, output position) and block of COB output channels (blockIdx.y); w is the reference's [c_out][kg].
 template <int COB>
-__global__ __launch_bounds__(UD_THREADS) void conv2d_direct_kernel(Conv2dArgs c) {
-    const long long col = (long long)blockIdx.x * UD_THREADS + threadIdx.x;
+__global__ __launch_bounds__(CG_THREADS) void conv2d_direct_kernel(Conv2dArgs c) {
+    const long long col = (long long)blockIdx.x * CG_THREADS + threadIdx.x;
     if (col >= c.n_cols) return;
     const int co0 = blockIdx.y * COB;
     const long long item = col / c.hw_out, rem = col - item * c.hw_out;
@@ -257,7 +176,7 @@ __global__ __launch_bounds__(UD_THREADS) void conv2d_direct_kernel(Conv2dArgs c)
     for (int q = 0; q < COB; ++q)
         if (co0 + q < c.c_out) {
             const float bias = c.bias ? c.bias[co0 + q] : 0.f;
-            yb[(long long)q * c.hw_out] = ud_act(s[q] + bias, c);
+            yb[(long long)q * c.hw_out] = cg_act(s[q] + bias, c.act, c.slope);
         }
 }
 
@@ -265,8 +184,8 @@ template <int WM, int WN, int TM, int TN>
 static void launch_conv2d_gemm(const Conv2dArgs& c, hipStream_t s) {
     constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
     const dim3 grid((unsigned)((c.n_cols + BN - 1) / BN), (unsigned)((c.c_out + BM - 1) / BM), 1);
-    const size_t tab = (size_t)((c.kg + UD_KT - 1) / UD_KT) * UD_KT * sizeof(int2);
-    hipLaunchKernelGGL((conv2d_gemm_kernel<WM, WN, TM, TN>), grid, dim3(UD_THREADS), tab, s, c);
+    const size_t tab = (size_t)((c.kg + CG_KT - 1) / CG_KT) * CG_KT * sizeof(int2);
+    hipLaunchKernelGGL((conv2d_gemm_kernel<WM, WN, TM, TN>), grid, dim3(CG_THREADS), tab, s, c);
 }
 
 static int ud_log2(int n) { int l = 0; while ((1 << l) < n) ++l; return l; }
@@ -317,8 +236,8 @@ extern "C" int adk_conv2d(const float* x, const float* w, const float* bias, flo
                           int32_t act, float slope, int32_t impl, void* stream) {
     if (n_items < 0 || c_in <= 0 || h_in <= 0 || w_in <= 0 || c_out <= 0 || kh <= 0 || kw <= 0 || sh <= 0 || sw <= 0 || ph < 0 || pw < 0)
         return fail(ADK_ERR_ARG, "adk_conv2d: need n_items >= 0, c_in, h_in, w_in, c_out, kh, kw, sh, sw > 0, ph, pw >= 0");
-    if (act != UD_ACT_NONE && act != UD_ACT_LEAKY) return fail(ADK_ERR_ARG, "adk_conv2d: act must be 0 (none) or 2 (leaky)");
-    if (impl != UD_IMPL_DIRECT && impl != UD_IMPL_GEMM) return fail(ADK_ERR_ARG, "adk_conv2d: impl must be 1 (direct) or 2 (gemm)");
+    if (act != CG_ACT_NONE && act != CG_ACT_LEAKY) return fail(ADK_ERR_ARG, "adk_conv2d: act must be 0 (none) or 2 (leaky)");
+    if (impl != CG_IMPL_DIRECT && impl != CG_IMPL_GEMM) return fail(ADK_ERR_ARG, "adk_conv2d: impl must be 1 (direct) or 2 (gemm)");
     if (kh >= 32768 || kw >= 32768) return fail(ADK_ERR_ARG, "adk_conv2d: kernel too large");
     const long long span_h = (long long)h_in + 2LL * ph - kh, span_w = (long long)w_in + 2LL * pw - kw;
     if (span_h < 0 || span_w < 0) return fail(ADK_ERR_SHAPE, "adk_conv2d: kernel larger than the padded input");
@@ -338,8 +257,8 @@ extern "C" int adk_conv2d(const float* x, const float* w, const float* bias, flo
     c.h_out = (int)h_out; c.w_out = (int)w_out; c.act = act; c.slope = slope; c.kg = (int)kg;
     c.hw_in = (long long)h_in * w_in; c.hw_out = h_out * w_out;
     c.n_cols = (long long)n_items * c.hw_out;
-    if (impl == UD_IMPL_DIRECT) {
-        if ((c.n_cols + UD_THREADS - 1) / UD_THREADS >= (1LL << 31) || (c_out + 7) / 8 > 65535)
+    if (impl == CG_IMPL_DIRECT) {
+        if ((c.n_cols + CG_THREADS - 1) / CG_THREADS >= (1LL << 31) || (c_out + 7) / 8 > 65535)
             return fail(ADK_ERR_ARG, "adk_conv2d: layer too large for the direct kernel");
     } else {
         if (kg > UD_MAX_K) return fail(ADK_ERR_ARG, "adk_conv2d: c_in * kh * kw > 4096 is beyond the gemm kernel's tap table");
@@ -349,10 +268,10 @@ extern "C" int adk_conv2d(const float* x, const float* w, const float* bias, flo
     if (n_items == 0) return ADK_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
     DeviceGuard guard(device_of(y));
-    if (impl == UD_IMPL_DIRECT) {
-        const unsigned nb = (unsigned)((c.n_cols + UD_THREADS - 1) / UD_THREADS);
-        if (c_out >= 8) hipLaunchKernelGGL(conv2d_direct_kernel<8>, dim3(nb, (unsigned)((c_out + 7) / 8)), dim3(UD_THREADS), 0, s, c);
-        else hipLaunchKernelGGL(conv2d_direct_kernel<1>, dim3(nb, (unsigned)c_out), dim3(UD_THREADS), 0, s, c);
+    if (impl == CG_IMPL_DIRECT) {
+        const unsigned nb = (unsigned)((c.n_cols + CG_THREADS - 1) / CG_THREADS);
+        if (c_out >= 8) hipLaunchKernelGGL(conv2d_direct_kernel<8>, dim3(nb, (unsigned)((c_out + 7) / 8)), dim3(CG_THREADS), 0, s, c);
+        else hipLaunchKernelGGL(conv2d_direct_kernel<1>, dim3(nb, (unsigned)c_out), dim3(CG_THREADS), 0, s, c);
     } else {
         launch_conv2d_gemm<1, 4, 1, 1>(c, s);                          // 32 x 128; wider c_out takes more grid rows
     }

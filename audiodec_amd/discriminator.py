@@ -33,7 +33,21 @@ LOSS_MSE_ONE, LOSS_SQ, LOSS_L1, LOSS_SUM, LOSS_HINGE_REAL, LOSS_HINGE_FAKE = 0, 
 
 # one conv layer: key = state-dict prefix of its nn.Conv (".weight" etc. follow), act_slope None = no activation,
 # norm "none" | "weight" | "spectral", conv2d = a (kernel, 1) Conv2d of the period discriminator
-Layer = namedtuple("Layer", "key cin cout kernel stride pad groups bias act_slope norm conv2d")
+class Layer(namedtuple("Layer", "key cin cout kernel stride pad groups bias act_slope norm conv2d")):
+    """A layer description says what loading needs of it: ``weight_shape``, ``fold`` (the state dict's weight in that shape's
+    rank) and ``conv``, the holder of its device weights."""
+    __slots__ = ()
+
+    @property
+    def weight_shape(self):
+        return (self.cout, self.cin // self.groups, self.kernel)
+
+    def fold(self, w):
+        return w.reshape(w.shape[0], w.shape[1], w.shape[2]) if self.conv2d else w
+
+    def conv(self, w, b, dev):
+        return _Conv(self, w, b, dev)
+
 
 SCALE_DEFAULTS = dict(in_channels=1, out_channels=1, kernel_sizes=[15, 41, 5, 3], channels=128, max_downsample_channels=1024,
                       max_groups=16, bias=True, downsample_scales=[2, 2, 4, 4, 1], nonlinear_activation="LeakyReLU",
@@ -127,7 +141,8 @@ def conv_impl(layer):
 
 
 def effective_weight(sd, layer):
-    """(C_out, C_in/g, k) float32 CPU weight of one layer from a reference state dict (weight norm folded)."""
+    """``layer.weight_shape`` float32 CPU weight of one layer from a reference state dict (weight norm folded): (C_out, C_in/g, k),
+    or (C_out, C_in, kh, kw) for a spectral layer."""
     k = layer.key
     if f"{k}.weight_orig" in sd or f"{k}.weight_u" in sd:
         raise NotImplementedError(f"{k}: spectral-norm parameters (weight_orig / weight_u) are not implemented on the HIP path")
@@ -135,10 +150,8 @@ def effective_weight(sd, layer):
         w = torch._weight_norm(sd[f"{k}.weight_v"].float(), sd[f"{k}.weight_g"].float(), 0)
     else:
         w = sd[f"{k}.weight"].float()
-    w = w.detach().cpu()
-    if layer.conv2d:
-        w = w.reshape(w.shape[0], w.shape[1], w.shape[2])
-    exp = (layer.cout, layer.cin // layer.groups, layer.kernel)
+    w = layer.fold(w.detach().cpu())
+    exp = layer.weight_shape
     if tuple(w.shape) != exp:
         raise ValueError(f"{k}: weight shape {tuple(w.shape)} does not match the configured {exp}")
     return w.contiguous()
@@ -199,20 +212,24 @@ def _prep(x, rows, n_in, op, a, b=0, c=0, n_out=None):
 
 
 class _Module:
-    """Shared device handling and state-dict loading of a set of layers."""
+    """Device handling and state-dict loading of a set of layers, of the spectral discriminators' window buffers, and of the
+    sub-discriminators (children) that compute with this module's weights."""
 
-    def _init_layers(self, layers, device):
+    def _init_layers(self, layers, device, windows=(), children=()):
         self._layers = layers
-        self._convs = None
+        self._window_shapes = list(windows)           # [(state-dict key, expected shape)]
+        self._children = list(children)
+        self._host = self._host_windows = self._convs = self._windows = None
         self._dev = torch.device(device) if device is not None else None
         if self._dev is not None:
             native.require_gpu(self._dev)
 
     def state_dict_keys(self):
-        return [k for L in self._layers for k in expected_keys(L)]
+        return [k for k, _ in self._window_shapes] + [k for L in self._layers for k in expected_keys(L)]
 
     def load_state_dict(self, state_dict, strict=True):
-        """Reference keys (spectral-norm keys raise NotImplementedError); weight norm is folded here, once."""
+        """Reference keys (spectral-norm keys raise NotImplementedError); weight norm is folded here, once; the window buffers
+        are kept as loaded."""
         sd = dict(state_dict)
         for k in sd:
             if k.endswith(".weight_orig") or k.endswith(".weight_u"):
@@ -224,7 +241,14 @@ class _Module:
             raise RuntimeError(f"Error(s) in loading state_dict for {type(self).__name__}: missing keys {missing}, "
                                f"unexpected keys {unexpected}")
         self._host = [(L, effective_weight(sd, L), sd[f"{L.key}.bias"] if L.bias else None) for L in self._layers]
+        self._host_windows = {}
+        for key, shape in self._window_shapes:
+            w = sd[key].detach().float().cpu().contiguous()
+            if tuple(w.shape) != shape:
+                raise ValueError(f"{key}: window shape {tuple(w.shape)} does not match win_length {shape[0]}")
+            self._host_windows[key] = w
         self._convs = None
+        self._hand_down()
         if self._dev is not None:
             self.to(self._dev)
         return self
@@ -234,9 +258,26 @@ class _Module:
         native.require_gpu(dev)
         if self._dev != dev or self._convs is None:
             self._dev = dev
-            if getattr(self, "_host", None) is not None:
-                self._convs = {L.key: _Conv(L, w, b, dev) for L, w, b in self._host}
+            if self._host is not None:
+                self._convs = {L.key: L.conv(w, b, dev) for L, w, b in self._host}
+                self._windows = {k: w.to(dev) for k, w in self._host_windows.items()}
+        self._share()
         return self
+
+    def _hand_down(self):
+        """Children see their own slice of the loaded weights, so each can also be called by itself."""
+        for m in self._children:
+            own = set(m._layers)
+            m._host = [h for h in self._host if h[0] in own]
+            m._host_windows = {k: self._host_windows[k] for k, _ in m._window_shapes}
+            m._convs = None
+            m._hand_down()
+
+    def _share(self):
+        """Children compute with this module's device tensors."""
+        for m in self._children:
+            m._dev, m._convs, m._windows = self._dev, self._convs, self._windows
+            m._share()
 
     @property
     def device(self):
@@ -251,12 +292,12 @@ class _Module:
     def _prepare(self, x):
         _no_grad_inputs(x)
         x = _settled(x)
-        if getattr(self, "_host", None) is None:
+        if self._host is None:
             raise RuntimeError(f"{type(self).__name__}: no weights loaded (call load_state_dict first)")
-        if self._dev is None:
-            self.to(x.device if x.device.type == "cuda" else torch.device("cuda", torch.cuda.current_device()))
+        self._prepare_device(x)
         if self._convs is None:
             self.to(self._dev)
+        self._share()
         if x.dim() != 3:
             raise ValueError(f"expected a (B, C, T) input, got shape {tuple(x.shape)}")
         return x.to(device=self._dev, dtype=torch.float32).contiguous()
@@ -354,28 +395,15 @@ class Discriminator(_Module):
                                                   discriminator_params=scale_discriminator_params,
                                                   follow_official_norm=follow_official_norm, _prefix="msd.")
         self.mpd = HiFiGANMultiPeriodDiscriminator(periods=periods, discriminator_params=period_discriminator_params, _prefix="mpd.")
-        self._init_layers(self.msd._layers + self.mpd._layers, device)
+        self.discriminator_layers = self.msd.discriminator_layers + self.mpd.discriminator_layers
+        self._init_layers(self.msd._layers + self.mpd._layers, device, children=[self.msd, self.mpd])
 
     @property
     def n_discriminators(self):
-        return len(self.msd.discriminator_layers) + len(self.mpd.discriminator_layers)
-
-    def load_state_dict(self, state_dict, strict=True):
-        super().load_state_dict(state_dict, strict)
-        for m in (self.msd, self.mpd):
-            m._host = [h for h in self._host if h[0] in set(m._layers)]
-        return self
-
-    def to(self, device):
-        super().to(device)
-        for m in (self.msd, self.mpd):
-            m._dev, m._convs = self._dev, self._convs
-        return self
+        return len(self.discriminator_layers)
 
     def layers_of(self, x):
         x = self._prepare(x)
-        for m in (self.msd, self.mpd):
-            m._dev, m._convs = self._dev, self._convs
         b, c, t = x.shape
         if c != 1:
             x = x.reshape(b * c, 1, t)
@@ -563,8 +591,7 @@ class AdversarialEval:
         self._totals = None
 
     def _layout(self):
-        d = self.discriminator
-        subs = d.msd.discriminator_layers + d.mpd.discriminator_layers if isinstance(d, Discriminator) else d.discriminator_layers
+        subs = self.discriminator.discriminator_layers
         fm = [self.feat_match.layers_used(len(ls)) for ls in subs] if self.feat_match else []
         return len(subs), fm
 
@@ -661,9 +688,10 @@ def discriminator_for(model_type, discriminator_params, device=None):
     raise NotImplementedError(f"Model type: {model_type} is not supported for the discriminator!")
 
 
-def load_discriminator(checkpoint, device=None):
+def load_discriminator(checkpoint, device=None, discriminator_for=discriminator_for):
     """The discriminator of a training checkpoint: config.yml next to it, torch.load(checkpoint)['model']['discriminator']
-    (trainer/trainerGAN.py:95-121).  The returned module's ``config`` is the parsed config.yml."""
+    (trainer/trainerGAN.py:95-121), built by ``discriminator_for`` (this module's: the HiFi-GAN model types only).  The returned
+    module's ``config`` is the parsed config.yml."""
     import yaml
     cfg_path = os.path.join(os.path.dirname(os.path.abspath(checkpoint)), "config.yml")
     with open(cfg_path) as f:

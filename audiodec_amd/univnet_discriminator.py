@@ -17,21 +17,33 @@ spectrogram uses the loaded window.  Weight norm (``weight_g``/``weight_v``) is 
 Forward only: an input that requires grad while grad is enabled raises NotImplementedError.
 """
 import copy
-import os
 from collections import namedtuple
 
 import torch
 
 from . import discriminator as D
 from . import native
-from .discriminator import AdversarialEval, DiscriminatorAdversarialLoss, FeatureMatchLoss, GeneratorAdversarialLoss, from_config  # noqa: F401
+from .discriminator import (ACT_LEAKY, ACT_NONE, IMPL_DIRECT, IMPL_GEMM, MPD_DISC_DEFAULTS, AdversarialEval,  # noqa: F401
+                            DiscriminatorAdversarialLoss, FeatureMatchLoss, GeneratorAdversarialLoss, _Module, _ptr,
+                            effective_weight, expected_keys, from_config)
 
-ACT_NONE, ACT_LEAKY = D.ACT_NONE, D.ACT_LEAKY
-IMPL_DIRECT, IMPL_GEMM = D.IMPL_DIRECT, D.IMPL_GEMM
 GEMM_MAX_K = 4096                                     # adk_conv2d impl 2: c_in * kh * kw
 
+
 # one 2-D conv layer: kernel, stride, pad are (frames axis, bins axis); norm "none" | "weight"
-SpecLayer = namedtuple("SpecLayer", "key cin cout kernel stride pad bias act_slope norm")
+class SpecLayer(namedtuple("SpecLayer", "key cin cout kernel stride pad bias act_slope norm")):
+    __slots__ = ()
+
+    @property
+    def weight_shape(self):
+        return (self.cout, self.cin) + tuple(self.kernel)
+
+    def fold(self, w):
+        return w
+
+    def conv(self, w, b, dev):
+        return _Conv2d(self, w, b, dev)
+
 
 SPECTRAL_DEFAULTS = dict(kernel_sizes=[(3, 9), (3, 9), (3, 9), (3, 9), (3, 3), (3, 3)],
                          strides=[(1, 1), (1, 2), (1, 2), (1, 2), (1, 1), (1, 1)], channels=32, bias=True,
@@ -40,7 +52,6 @@ SPECTRAL_DEFAULTS = dict(kernel_sizes=[(3, 9), (3, 9), (3, 9), (3, 9), (3, 3), (
 MRSD_DISC_DEFAULTS = dict(channels=32, kernel_sizes=[(3, 9), (3, 9), (3, 9), (3, 9), (3, 3), (3, 3)],
                           strides=[(1, 1), (1, 2), (1, 2), (1, 2), (1, 1), (1, 1)], bias=True,
                           nonlinear_activation="LeakyReLU", nonlinear_activation_params={"negative_slope": 0.2})
-MPD_DISC_DEFAULTS = D.MPD_DISC_DEFAULTS
 
 
 def _pair(v, what):
@@ -57,9 +68,7 @@ def spectral_layers(prefix, **kw):
     if unknown:
         raise TypeError(f"UnivNetSpectralDiscriminator: unexpected arguments {sorted(unknown)}")
     p = dict(SPECTRAL_DEFAULTS, **kw)
-    if p["nonlinear_activation"] != "LeakyReLU":
-        raise NotImplementedError(f"nonlinear_activation {p['nonlinear_activation']!r}: the HIP discriminator implements LeakyReLU only")
-    slope = float((p["nonlinear_activation_params"] or {}).get("negative_slope", 0.01))
+    slope = D._slope(p["nonlinear_activation"], p["nonlinear_activation_params"])
     ks = [_pair(k, "kernel_sizes") for k in p["kernel_sizes"]]
     st = [_pair(s, "strides") for s in p["strides"]]
     assert len(ks) == len(st) and len(ks) >= 3
@@ -92,31 +101,6 @@ def min_samples(fft_size, win_length):
 def conv_impl(layer):
     """Kernel per layer: the direct kernel where a GEMM tile would be mostly padding (C_in = 1 or C_out = 1), else the GEMM."""
     return IMPL_DIRECT if layer.cin == 1 or layer.cout == 1 else IMPL_GEMM
-
-
-def effective_weight(sd, layer):
-    """(C_out, C_in, kh, kw) float32 CPU weight of one spectral layer from a reference state dict (weight norm folded)."""
-    k = layer.key
-    if f"{k}.weight_g" in sd:
-        w = torch._weight_norm(sd[f"{k}.weight_v"].float(), sd[f"{k}.weight_g"].float(), 0)
-    else:
-        w = sd[f"{k}.weight"].float()
-    w = w.detach().cpu()
-    exp = (layer.cout, layer.cin) + tuple(layer.kernel)
-    if tuple(w.shape) != exp:
-        raise ValueError(f"{k}: weight shape {tuple(w.shape)} does not match the configured {exp}")
-    return w.contiguous()
-
-
-def expected_keys(layer):
-    if isinstance(layer, SpecLayer):
-        k = layer.key
-        ks = [f"{k}.weight_g", f"{k}.weight_v"] if layer.norm == "weight" else [f"{k}.weight"]
-        return ks + ([f"{k}.bias"] if layer.bias else [])
-    return D.expected_keys(layer)
-
-
-_ptr = D._ptr
 
 
 class _Conv2d:
@@ -159,73 +143,9 @@ def spectrogram(x, window, fft_size, hop_size, win_length):
     return out
 
 
-class _Module(D._Module):
-    """discriminator._Module with 2-D spectral layers and window buffers next to the period discriminator's layers."""
-
-    def _init_spectral(self, specs):
-        self._specs = specs                           # [(window key, fft_size, hop_size, win_length)]
-        self._windows = None
-
-    def state_dict_keys(self):
-        return [s[0] for s in self._specs] + [k for L in self._layers for k in expected_keys(L)]
-
-    def load_state_dict(self, state_dict, strict=True):
-        """Reference keys; weight norm is folded here, once; the window buffers are kept as loaded."""
-        sd = dict(state_dict)
-        for k in sd:
-            if k.endswith(".weight_orig") or k.endswith(".weight_u"):
-                raise NotImplementedError(f"{k}: spectral-norm parameters are not implemented on the HIP discriminator")
-        want = self.state_dict_keys()
-        missing = [k for k in want if k not in sd]
-        wanted = set(want)
-        unexpected = [k for k in sd if k not in wanted]
-        if missing or (strict and unexpected):
-            raise RuntimeError(f"Error(s) in loading state_dict for {type(self).__name__}: missing keys {missing}, "
-                               f"unexpected keys {unexpected}")
-        self._host = [(L, effective_weight(sd, L) if isinstance(L, SpecLayer) else D.effective_weight(sd, L),
-                       sd[f"{L.key}.bias"] if L.bias else None) for L in self._layers]
-        self._host_windows = {}
-        for key, _, _, win in self._specs:
-            w = sd[key].detach().float().cpu().contiguous()
-            if tuple(w.shape) != (win,):
-                raise ValueError(f"{key}: window shape {tuple(w.shape)} does not match win_length {win}")
-            self._host_windows[key] = w
-        self._convs = None
-        self._hand_down()
-        if self._dev is not None:
-            self.to(self._dev)
-        return self
-
-    def to(self, device):
-        dev = torch.device(device)
-        native.require_gpu(dev)
-        if self._dev != dev or self._convs is None:
-            self._dev = dev
-            if getattr(self, "_host", None) is not None:
-                self._convs = {L.key: (_Conv2d if isinstance(L, SpecLayer) else D._Conv)(L, w, b, dev) for L, w, b in self._host}
-                self._windows = {k: w.to(dev) for k, w in self._host_windows.items()}
-        self._share()
-        return self
-
-    def _children(self):
-        return []
-
-    def _hand_down(self):
-        """Sub-discriminators see their own slice of the loaded weights, so each can also be called by itself."""
-        for m in self._children():
-            own = set(m._layers)
-            m._host = [h for h in self._host if h[0] in own]
-            if isinstance(m, _Module):
-                m._host_windows = {s[0]: self._host_windows[s[0]] for s in m._specs}
-                m._hand_down()
-
-    def _share(self):
-        """Sub-discriminators compute with this module's device tensors."""
-        for m in self._children():
-            m._dev, m._convs = self._dev, self._convs
-            if isinstance(m, _Module):
-                m._windows = self._windows
-                m._share()
+def _window_shapes(specs):
+    """discriminator._Module's window list of specs = [(window key, fft_size, hop_size, win_length)]."""
+    return [(key, (win,)) for key, _, _, win in specs]
 
 
 def _check_window(window):
@@ -263,8 +183,8 @@ class UnivNetSpectralDiscriminator(_Module):
                                       nonlinear_activation=nonlinear_activation,
                                       nonlinear_activation_params=nonlinear_activation_params, use_weight_norm=use_weight_norm)
         self.discriminator_layers = [self.layers]
-        self._init_layers(list(self.layers), device)
-        self._init_spectral([(self.window_key, self.fft_size, self.hop_size, self.win_length)])
+        self._specs = [(self.window_key, self.fft_size, self.hop_size, self.win_length)]
+        self._init_layers(list(self.layers), device, windows=_window_shapes(self._specs))
 
     def output_shapes(self, n, t):
         """Shapes of the per-layer outputs for an (n, 1, t) input."""
@@ -303,11 +223,9 @@ class UnivNetMultiResolutionSpectralDiscriminator(_Module):
                                                                     win_length=win_lengths[i], window=window,
                                                                     _prefix=f"{_prefix}discriminators.{i}.", **params))
         self.discriminator_layers = [d.layers for d in self.discriminators]
-        self._init_layers([L for ls in self.discriminator_layers for L in ls], device)
-        self._init_spectral([s for d in self.discriminators for s in d._specs])
-
-    def _children(self):
-        return self.discriminators
+        self._specs = [s for d in self.discriminators for s in d._specs]
+        self._init_layers([L for ls in self.discriminator_layers for L in ls], device, windows=_window_shapes(self._specs),
+                          children=self.discriminators)
 
     def layers_of(self, x, d0=0, prepared=False):
         if not prepared:
@@ -315,7 +233,6 @@ class UnivNetMultiResolutionSpectralDiscriminator(_Module):
             if x.shape[1] != 1:
                 raise ValueError(f"expected a (B, 1, T) input, got {tuple(x.shape)}")
             _check_length(x.shape[2], self._specs)
-        self._share()
         for i, d in enumerate(self.discriminators):
             yield from d.layers_of(x, d0 + i, prepared=True)
 
@@ -333,15 +250,13 @@ class Discriminator(_Module):
                                                                 _prefix="mrsd.")
         self.mpd = D.HiFiGANMultiPeriodDiscriminator(periods=periods, discriminator_params=period_discriminator_params, _prefix="mpd.")
         self.discriminator_layers = self.mrsd.discriminator_layers + self.mpd.discriminator_layers
-        self._init_layers(self.mrsd._layers + self.mpd._layers, device)
-        self._init_spectral(self.mrsd._specs)
+        self._specs = self.mrsd._specs
+        self._init_layers(self.mrsd._layers + self.mpd._layers, device, windows=_window_shapes(self._specs),
+                          children=[self.mrsd, self.mpd])
 
     @property
     def n_discriminators(self):
         return len(self.discriminator_layers)
-
-    def _children(self):
-        return [self.mrsd, self.mpd]
 
     def layers_of(self, x):
         D._no_grad_inputs(x)
@@ -351,7 +266,6 @@ class Discriminator(_Module):
                                  "conv (the spectrogram of a (B, C, T) input has C channels, the conv expects 1); set flat_channel=True")
             _check_length(x.shape[2], self._specs)
         x = self._prepare(x)
-        self._share()
         b, c, t = x.shape
         if c != 1:
             x = x.reshape(b * c, 1, t)
@@ -367,15 +281,5 @@ def discriminator_for(model_type, discriminator_params, device=None):
 
 
 def load_discriminator(checkpoint, device=None):
-    """The discriminator of a training checkpoint of any of the four model types: config.yml next to it,
-    torch.load(checkpoint)['model']['discriminator'] (trainer/trainerGAN.py:95-121).  The returned module's ``config`` is the
-    parsed config.yml."""
-    import yaml
-    cfg_path = os.path.join(os.path.dirname(os.path.abspath(checkpoint)), "config.yml")
-    with open(cfg_path) as f:
-        config = yaml.load(f, Loader=yaml.Loader)
-    disc = discriminator_for(config.get("model_type", "symAudioDec"), config.get("discriminator_params", {}), device=device)
-    state = torch.load(checkpoint, map_location="cpu", weights_only=False)
-    disc.load_state_dict(state["model"]["discriminator"])
-    disc.config = config
-    return disc
+    """discriminator.load_discriminator for a training checkpoint of any of the four model types."""
+    return D.load_discriminator(checkpoint, device, discriminator_for)

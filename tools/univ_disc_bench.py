@@ -80,13 +80,11 @@ def main():
     ap.add_argument("--hip-only", action="store_true", help="run only the HIP leg (for a kernel trace of its own)")
     a = ap.parse_args()
     import univ_disc_oracle as UO
-    from audiodec_amd import discriminator as D
     from audiodec_amd import univnet_discriminator as U
     dev = "cuda:0"
     sd = UO.state_dict("v3")
     d = U.Discriminator(**UO.PARAMS["v3"], device=dev).load_state_dict(sd)
-    ws = {L.key: ((U.effective_weight if isinstance(L, U.SpecLayer) else D.effective_weight)(sd, L).to(dev), sd[L.key + ".bias"].to(dev))
-          for L in d._layers}
+    ws = {L.key: (U.effective_weight(sd, L).to(dev), sd[L.key + ".bias"].to(dev)) for L in d._layers}
     ws.update({k: sd[k].to(dev) for k, _, _, _ in d._specs})
     cfg = {"generator_adv_loss_params": {"average_by_discriminators": False},
            "discriminator_adv_loss_params": {"average_by_discriminators": False}, "use_feat_match_loss": True,
