@@ -86,7 +86,8 @@ def _settled(t):
 
 def _no_grad_inputs(*ts):
     if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in ts):
-        raise NotImplementedError("the HIP mel-spectrogram loss is forward only: run it under torch.no_grad() or detach the inputs")
+        raise NotImplementedError("the HIP metric losses (mel, STFT, shape) are forward only: run them under torch.no_grad() or "
+                                  "detach the inputs")
 
 
 def _signals(x, device):

@@ -146,6 +146,19 @@ class TestMain:
             self.mel_loss = mel.from_config(self.encoder_config, device=self.device)
             if self.mel_loss is None:
                 raise ValueError(f"--mel_distance: the encoder config of {args.encoder} enables no mel loss (use_mel_loss)")
+        # opt-in (--stft_distance, --shape_distance): the encoder config's stft_loss_params / shape_loss_params; the flag is the
+        # opt-in, so use_stft_loss / use_shape_loss are not consulted
+        self.stft_loss = self.mean_stft_distance = self.shape_loss = self.mean_shape_distance = None
+        if bool(getattr(args, "stft_distance", False)):
+            from . import stft_loss
+            if "stft_loss_params" not in self.encoder_config:
+                raise ValueError(f"--stft_distance: the encoder config of {args.encoder} has no stft_loss_params")
+            self.stft_loss = stft_loss.MultiResolutionSTFTLoss(**self.encoder_config["stft_loss_params"], device=self.device)
+        if bool(getattr(args, "shape_distance", False)):
+            from . import waveform_loss
+            if "shape_loss_params" not in self.encoder_config:
+                raise ValueError(f"--shape_distance: the encoder config of {args.encoder} has no shape_loss_params")
+            self.shape_loss = waveform_loss.MultiWindowShapeLoss(**self.encoder_config["shape_loss_params"])
 
     def load_dataset(self, subset, subset_num):
         data_path = os.path.join(self.encoder_config["data"]["path"], self.encoder_config["data"]["subset"][subset])
@@ -203,7 +216,7 @@ class TestMain:
     def run(self):
         """bin/test.py:86-104: per-utterance RTF = wall time / audio duration, averaged over utterances."""
         total_rtf, idx = 0.0, 0
-        mel_lines = []
+        mel_lines, stft_lines, shape_lines = [], [], []
         with torch.no_grad():
             for idx, (utt_id, x) in enumerate(self.dataset, 1):
                 start = time.time()
@@ -215,6 +228,10 @@ class TestMain:
                 total_rtf += rtf
                 if self.mel_loss is not None:                                 # outside the RTF timing, before PCM-16
                     mel_lines.append((utt_id, self.utterance_mel_distance(x, y_dev)))
+                if self.stft_loss is not None:
+                    stft_lines.append((utt_id,) + self.utterance_stft_distance(x, y_dev))
+                if self.shape_loss is not None:
+                    shape_lines.append((utt_id, self.utterance_shape_distance(x, y_dev)))
                 write_wav_pcm16(os.path.join(self.outdir, f"{utt_id}_output.wav"), y, self.decoder_config["sampling_rate"])
         self.mean_rtf = total_rtf / idx
         logging.info("Finished generation of %d utterances (RTF = %.03f)." % (idx, self.mean_rtf))
@@ -225,14 +242,41 @@ class TestMain:
                     f.write(f"{utt_id} {v:.9g}\n")
                 f.write(f"mean {self.mean_mel_distance:.9g}\n")
             logging.info("Mel distance of %d utterances: mean %.06f." % (idx, self.mean_mel_distance))
+        if self.stft_loss is not None:
+            self.mean_stft_distance = (float(np.mean([sc for _, sc, _ in stft_lines])), float(np.mean([m for _, _, m in stft_lines])))
+            with open(os.path.join(self.outdir, "stft_distance.txt"), "w") as f:
+                for utt_id, sc, m in stft_lines:
+                    f.write(f"{utt_id} {sc:.9g} {m:.9g}\n")
+                f.write("mean %.9g %.9g\n" % self.mean_stft_distance)
+            logging.info("STFT distance of %d utterances: mean sc %.06f, mag %.06f." % ((idx,) + self.mean_stft_distance))
+        if self.shape_loss is not None:
+            self.mean_shape_distance = float(np.mean([v for _, v in shape_lines]))
+            with open(os.path.join(self.outdir, "shape_distance.txt"), "w") as f:
+                for utt_id, v in shape_lines:
+                    f.write(f"{utt_id} {v:.9g}\n")
+                f.write(f"mean {self.mean_shape_distance:.9g}\n")
+            logging.info("Shape distance of %d utterances: mean %.06f." % (idx, self.mean_shape_distance))
         return self.mean_rtf
+
+    def _scored_pair(self, audio, y):
+        """The float output y (C, 1, T') and the input audio (T, C) as (C, 1, T), both cropped to the shorter length."""
+        x = _streams_of(audio, self.multi_channel).to(self.device)
+        n = min(x.shape[-1], y.shape[-1])
+        return y[..., :n], x[..., :n]
 
     def utterance_mel_distance(self, audio, y):
         """The encoder config's mel loss between the input audio (T, C) and the float output y (C, 1, T') cropped to the
         input's length."""
-        x = _streams_of(audio, self.multi_channel).to(self.device)
-        n = min(x.shape[-1], y.shape[-1])
-        return float(self.mel_loss(y[..., :n], x[..., :n]))
+        return float(self.mel_loss(*self._scored_pair(audio, y)))
+
+    def utterance_stft_distance(self, audio, y):
+        """(sc, mag) of the encoder config's multi-resolution STFT loss, output against input."""
+        sc, mag = self.stft_loss(*self._scored_pair(audio, y))
+        return float(sc), float(mag)
+
+    def utterance_shape_distance(self, audio, y):
+        """The encoder config's waveform-shape loss, output against input."""
+        return float(self.shape_loss(*self._scored_pair(audio, y)))
 
 
 def _partial_fit(state, X):

@@ -21,6 +21,10 @@ def main():
     parser.add_argument("--specific_folder", choices=("True", "False"), default="False")
     parser.add_argument("--mel_distance", action="store_true",
                         help="also score each utterance with the encoder config's mel-spectrogram loss (mel_distance.txt)")
+    parser.add_argument("--stft_distance", action="store_true",
+                        help="also score each utterance with the encoder config's stft_loss_params (stft_distance.txt: sc mag)")
+    parser.add_argument("--shape_distance", action="store_true",
+                        help="also score each utterance with the encoder config's shape_loss_params (shape_distance.txt)")
     args = parser.parse_args()
 
     test_main = TestMain(args=args)

@@ -306,6 +306,41 @@ int adk_conv2d(const float* x, const float* w, const float* bias, float* y, int3
                float slope, int32_t impl, void* stream);
 
 /*
+ * Multi-resolution STFT loss and waveform-shape loss, one resolution / one window length per call (losses/stft_loss.py:19-170,
+ * losses/waveform_loss.py:15-75).  The STFT is adk_logmel's: torch.stft's defaults, the window [win_length] centred in n_fft,
+ * 1 + n_samples/hop frames, n_fft/2 + 1 bins, mag = sqrt(max(re^2 + im^2, eps)) (a NaN stays NaN).
+ * adk_stft_mag writes out [n_signals][frames][n_fft/2 + 1] f32 (the layout stft() returns in the reference).
+ * adk_stft_distance (x predicted, y ground truth, both [n_signals][n_samples]) FOLDS into a caller-owned accumulator on the
+ * device (zero it to start; nothing is cleared here), never writing a magnitude:
+ *   sums [3] double += { sum d^2 with d = y_mag - x_mag in f32,  sum y_mag^2,  sum |log y_mag - log x_mag| (correctly rounded f32 logs, f32 difference) }
+ *   count [1] int64 += n_signals * frames * (n_fft/2 + 1)
+ * and, from the totals after this call's fold, writes sc [1] f32 = sqrt(sums[0]) / sqrt(sums[1]) and mag [1] f32 = sums[2] / count
+ * (each may be NULL; NaN while count == 0).  adk_mag_distance folds the same three sums over two given magnitude tensors of n
+ * elements (SpectralConvergenceLoss / LogSTFTMagnitudeLoss take magnitudes), count += n.
+ * adk_shape_distance: with windows = n_samples / winlen (the tail is dropped), a = max |y_hat| and b = max |y| over each window (a
+ * NaN in the window gives NaN, as MaxPool1d):  sum [1] double += sum |a - b| (f32 difference);  count [1] int64 += n_signals *
+ * windows;  loss [1] f32 (or NULL) = sum / count (NaN while count == 0).  One lane owns a window when winlen < 64, else the 64
+ * lanes of a wave share it.
+ * n_signals == 0 (n == 0) folds nothing.  workspace: the matching *_workspace_bytes bytes, 8-byte aligned, any contents (NULL when
+ * that size is 0).  Per-workgroup f64 partials (at most 2048 workgroups, a function of the shape only) and a fixed-order
+ * finalize launch: bitwise reproducible.  Calls on one accumulator must be ordered (one stream).  Limits: n_fft a power of two
+ * in [256, 4096], 0 < win_length <= n_fft, hop > 0, n_samples > n_fft/2; winlen > 0, n_samples >= winlen.  Every argument is
+ * checked before any HIP call (ADK_ERR_ARG).  No allocation, no synchronisation.
+ */
+int64_t adk_stft_workspace_bytes(int32_t n_signals, int32_t n_samples, int32_t n_fft, int32_t hop);
+int adk_stft_mag(const float* x, int32_t n_signals, int32_t n_samples, int32_t n_fft, int32_t hop, const float* window,
+                 int32_t win_length, float eps, float* out, void* stream);
+int adk_stft_distance(const float* x, const float* y, int32_t n_signals, int32_t n_samples, int32_t n_fft, int32_t hop,
+                      const float* window, int32_t win_length, float eps, double* sums, int64_t* count, void* workspace,
+                      float* sc, float* mag, void* stream);
+int64_t adk_mag_distance_workspace_bytes(int64_t n);
+int adk_mag_distance(const float* x_mag, const float* y_mag, int64_t n, double* sums, int64_t* count, void* workspace, float* sc,
+                     float* mag, void* stream);
+int64_t adk_shape_workspace_bytes(int32_t n_signals, int32_t n_samples, int32_t winlen);
+int adk_shape_distance(const float* y_hat, const float* y, int32_t n_signals, int32_t n_samples, int32_t winlen, double* sum,
+                       int64_t* count, void* workspace, float* loss, void* stream);
+
+/*
  * Bit-packed code wire format (the reference passes the int64 index tensor through a
  * queue.Queue, bin/stream.py:224,230, and never serialises it).  One frame of one stream = n_q codes of
  * `bits` bits, LSB-first: code q (= emitted index - size*q) occupies bits [q*bits, (q+1)*bits) of the
