@@ -178,6 +178,11 @@ extern "C" int adk_set_option(const char* name, int32_t value) {
         if (r == 0) return ADK_OK;
         if (r < 0) return fail(ADK_ERR_ARG, std::string("adk_set_option: bad value for ") + name);
     }
+    {
+        const int r = rvq_ema_set_option(name, value);
+        if (r == 0) return ADK_OK;
+        if (r < 0) return fail(ADK_ERR_ARG, std::string("adk_set_option: bad value for ") + name);
+    }
     return fail(ADK_ERR_ARG, std::string("adk_set_option: unknown option ") + name);
 }
 

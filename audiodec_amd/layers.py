@@ -3,7 +3,8 @@
 ``CausalConv1d`` / ``CausalConvTranspose1d`` expose the reference's constructor arguments and the
 streaming ``inference`` / ``reset_buffer`` methods (conv_layer.py:118-159, 162-200) on top of
 ``adk_causal_conv`` with a private state ring; ``ResidualVQ`` exposes ``forward`` / ``forward_index`` / ``initial``
-/ ``lookup`` (vq_module.py:119-161) on top of ``adk_rvq_encode`` / ``adk_rvq_stats`` / ``adk_rvq_lookup``.  The model
+/ ``lookup`` / ``train`` (vq_module.py:61-161) on top of ``adk_rvq_encode`` / ``adk_rvq_stats`` / ``adk_rvq_lookup`` /
+``adk_rvq_ema_update``.  The model
 programs (program.py) do not go through these objects -- they exist so single layers can be used and
 tested against the reference's layer classes one to one.
 
@@ -183,19 +184,41 @@ class CausalConvTranspose1d(_CausalBase):
 
 
 class ResidualVQ:
-    """Residual VQ (layers/vq_module.py:107-161): forward (eval mode) / forward_index / initial / lookup."""
+    """Residual VQ (layers/vq_module.py:107-161): forward / forward_index / initial / lookup, and train() / eval().  In eval mode (the
+    default) forward is the reference's eval-mode forward; in training mode it also applies the reference's EMA codebook update
+    (vq_module.py:74-80, adk_rvq_ema_update) after computing its results against the table as it was."""
 
-    def __init__(self, embeds, device="cuda:0"):
-        """embeds: list of the reference's `embed` buffers, each (dim, codebook_size)."""
+    def __init__(self, embeds, device="cuda:0", cluster_size=None, embed_avg=None, decay=0.8, eps=1e-5):
+        """embeds: list of the reference's `embed` buffers, each (dim, codebook_size).  cluster_size / embed_avg: lists of the stages'
+        EMA buffers, (codebook_size,) and (dim, codebook_size); None: zeros and a copy of embed, as the reference initialises them."""
         self.dev = native.require_gpu(device)
         self.n_q = len(embeds)
         self.dim, self.codebook_size = embeds[0].shape
         emb = [e.detach().float().cpu() for e in embeds]
         self.embed = torch.stack(emb).contiguous().to(self.dev)
         self.enorm = torch.stack([e.pow(2).sum(0, keepdim=True)[0] for e in emb]).contiguous().to(self.dev)
-        self._emb_cpu = emb
+        self._emb_cpu = emb            # None once a training-mode forward has rewritten the table on the device
         self.codebook = None
         self._cb_rows = None           # private row-major copy for forward(): lookup() keeps needing initial(), as in the reference
+        self.training = False
+        self.decay, self.eps = float(decay), float(eps)
+        cs = [torch.zeros(self.codebook_size) for _ in emb] if cluster_size is None else [c.detach().float().cpu() for c in cluster_size]
+        ea = emb if embed_avg is None else [a.detach().float().cpu() for a in embed_avg]
+        self.cluster_size = torch.stack(cs).contiguous().to(self.dev)
+        self.embed_avg = torch.stack(ea).contiguous().to(self.dev)
+
+    def train(self, mode=True):
+        self.training = bool(mode)
+        return self
+
+    def eval(self):
+        return self.train(False)
+
+    def _row_major(self):
+        from . import codebook_usage
+        if self._emb_cpu is not None:
+            return codebook_usage.row_major_codebook(self._emb_cpu, self.dev)
+        return self.embed.transpose(1, 2).reshape(-1, self.dim).contiguous()
 
     def forward_index(self, x, flatten_idx=False):
         """x (B, T, dim) -> (quantized_out (B, T, dim), indices (n_q, B, T) squeezed at dim 1)."""
@@ -213,9 +236,11 @@ class ResidualVQ:
         return zq, idx.squeeze(1)
 
     def forward(self, x):
-        """ResidualVQ.forward in eval mode (vq_module.py:119-134): x (B, T, dim) -> (quantized_out (B, T, dim), losses (n_q,),
+        """ResidualVQ.forward (vq_module.py:119-134): x (B, T, dim) -> (quantized_out (B, T, dim), losses (n_q,),
         perplexities (n_q,)).  quantized_out is forward_index's (the same search); the per-stage commitment loss and code-histogram
-        perplexity come from adk_rvq_stats over the emitted codes.  Needs no initial(): the row-major codes are a private copy."""
+        perplexity come from adk_rvq_stats over the emitted codes.  Needs no initial(): the row-major codes are a private copy.
+        In training mode the EMA update of every stage follows (embed, enorm, cluster_size, embed_avg, and codebook if initial() was
+        called, are rewritten in place); the results are those against the table as it was."""
         from . import codebook_usage
         B, T, D = x.shape
         xt = x.to(self.dev, torch.float32).contiguous()
@@ -226,16 +251,28 @@ class ResidualVQ:
             C.c_void_p(idx.data_ptr()), C.c_void_p(zq.data_ptr()), B * T, self.n_q, self.dim, self.codebook_size,
             native.current_stream(self.dev)), "adk_rvq_encode")
         if self._cb_rows is None:
-            self._cb_rows = codebook_usage.row_major_codebook(self._emb_cpu, self.dev)
+            self._cb_rows = self._row_major()
         losses = torch.empty(self.n_q, dtype=torch.float32, device=self.dev)
         perplexities = torch.empty(self.n_q, dtype=torch.float32, device=self.dev)
         acc = codebook_usage.accumulator(self.n_q, self.codebook_size, self.dev)
         codebook_usage.fold(acc, xt.view(B * T, D), self._cb_rows, idx, self.n_q, self.dim, self.codebook_size, losses, perplexities)
+        if self.training:
+            from . import codebook_ema
+            if B * T == 0:
+                raise ValueError("forward: no rows to update the codebook from")
+            state = codebook_ema.State(self.embed, self.enorm, self._cb_rows, self.cluster_size, self.embed_avg)
+            codebook_ema.update(state, xt.view(B * T, D), idx, self.decay, self.eps)
+            self._emb_cpu = None
+            if self.codebook is not None:
+                self.codebook.copy_(self._cb_rows)
         return zq, losses, perplexities
 
     __call__ = forward
 
     def initial(self):
+        if self._emb_cpu is None:
+            self.codebook = self._row_major()
+            return
         cb = torch.stack([e.transpose(0, 1) for e in self._emb_cpu])
         self.codebook = cb.reshape(-1, cb.size(-1)).contiguous().to(self.dev)
 

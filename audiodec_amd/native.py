@@ -67,6 +67,8 @@ SYMBOLS = {
     "adk_rvq_lookup": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "adk_rvq_stats_workspace_bytes": (C.c_int64, [_i32, _i32]),
     "adk_rvq_stats": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "adk_rvq_ema_workspace_bytes": (C.c_int64, [_i32, _i32, _i32, _i32]),
+    "adk_rvq_ema_update": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "adk_mel_workspace_bytes": (C.c_int64, [_i32, _i32, _i32, _i32]),
     "adk_logmel": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, C.c_float, _vp, _vp]),
     "adk_mel_distance": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, C.c_float,

@@ -448,11 +448,33 @@ class AutoEncoderStreamGenerator(_StreamBase):
         idx = idx.reshape(self.n_q, B, T)
         return idx.squeeze(1) if B == 1 else idx
 
-    def quantizer_forward(self, z, return_stats=False):
+    def quantizer_forward(self, z, return_stats=False, ema=None):
         """Quantizer.forward in eval mode (quantizer.py:32-35 -> ResidualVQ.forward, vq_module.py:119-134):
         z (B, code_dim, T) -> zq (B, code_dim, T), the sum of the straight-through stage outputs.  return_stats=True returns
         (zq, vqloss (n_q,), perplexity (n_q,)) as Quantizer.forward does: the per-stage commitment loss and code-histogram
-        perplexity of this call's rows (adk_rvq_stats; zq is the same, bit for bit)."""
+        perplexity of this call's rows (adk_rvq_stats; zq is the same, bit for bit).
+        ema: a codebook_ema.CodebookEMA makes it Quantizer.forward in TRAINING mode -- the same returns, computed on THIS generator's
+        table as it was, then the EMA codebook update (ema.update) and ema.install() into this generator.  The ema's table must be the
+        one this generator uses (it was made from this generator, or install()ed here, and has no update that was not installed
+        here: ema.installed_in(self)); anything else is a ValueError, since the statistics would be folded with another table's codes
+        and install() would overwrite this generator's.  Such a call settles the call log first and is not logged itself: a guard
+        repair never applies an update twice."""
+        if ema is not None:
+            if not ema.installed_in(self):
+                raise ValueError("quantizer_forward(ema=...): this generator does not use the CodebookEMA's current table "
+                                 "(ema.install(generator) after its last update, or make the CodebookEMA from this generator)")
+            self.settle()
+            lg = lazy_guard.log_of(z)
+            if lg is not None:
+                lg.settle()
+            z = lazy_guard.plain(z)
+            flat = self._quantizer_forward_stats(z)            # [zq | vqloss | perplexity] on this generator's table, as without ema
+            B, D, T = z.shape
+            n = B * T * D
+            zq, vq, ppl = flat[:n].view(B, T, D).transpose(2, 1), flat[n:n + self.n_q], flat[n + self.n_q:]
+            ema.update(z)                                      # the same table, so the same search and codes
+            ema.install(self)
+            return (zq, vq, ppl) if return_stats else zq
         if not return_stats:
             return self._guarded(self._quantizer_forward, (z,), [], 0)
         out = self._guarded(self._quantizer_forward_stats, (z,), [], 0)

@@ -222,6 +222,33 @@ int adk_rvq_stats(const float* z, const float* codebook, const int64_t* idx, int
                   float* perplexity, void* stream);
 
 /*
+ * Residual VQ codebook update: the training branch of VectorQuantize.forward (layers/vq_module.py:74-80) for every stage of one
+ * ResidualVQ.forward, from the latents z [n_rows][dim] and the emitted indices idx [n_q][n_rows] (stage offset included) -- what
+ * adk_rvq_stats takes.  The residual entering stage s is rebuilt with adk_rvq_encode's f32 step from the OLD embed of every stage
+ * (the reference looks the codes up before a stage rewrites them), then per stage, all in f32 round-to-nearest, nothing contracted,
+ * with (float)decay and (float)(1.0 - decay):
+ *   cluster_size <- decay*cluster_size + (1-decay)*count_k
+ *   embed_avg    <- decay*embed_avg + (1-decay)*sum_{rows with code k} r_s       (the sum in f64, ascending row order, rounded once)
+ *   S = sum_k cluster_size (f64, fixed order);  smoothed_k = (cluster_size_k + eps) / (S + size*eps) * S
+ *   embed[:,k] = embed_avg[:,k] / smoothed_k
+ *   embed        [n_q][dim][size]   read (old codes), then overwritten
+ *   enorm        [n_q][size]        overwritten: |embed[:,k]|^2
+ *   codebook     [n_q*size][dim]    row-major twin of the new embed, overwritten; may be NULL
+ *   cluster_size [n_q][size], embed_avg [n_q][dim][size]   in/out
+ * so adk_rvq_encode / adk_rvq_lookup can follow on the same stream.  A code no row chose only decays (its quotient may grow large, as
+ * in the reference).  Bitwise reproducible and independent of the launch geometry (adk_set_option("rvq_ema_chunk_rows", n) moves it;
+ * 0 = default): no floating-point atomics.  An index outside its stage counts nothing, sums nothing, reads that stage's first code
+ * for the rest of the row's chain and raises bit 0 of adk_debug_flags().  workspace: adk_rvq_ema_workspace_bytes(...) bytes, 8-byte
+ * aligned, any contents, unused once the call's work has finished.  A stage whose cluster sizes are all zero and none of whose
+ * rows carries a code of that stage (every one flagged through bit 0) has S = 0: its smoothed sizes and embed become NaN, as the
+ * reference's would on an empty batch.  Limits: n_rows > 0, dim <= 128, n_q <= 16, n_q*size <= 2^28, 0 <= decay < 1, eps > 0.  Every argument is checked before any HIP call (ADK_ERR_ARG).
+ */
+int64_t adk_rvq_ema_workspace_bytes(int32_t n_rows, int32_t n_q, int32_t dim, int32_t size);
+int adk_rvq_ema_update(const float* z, const int64_t* idx, int32_t n_rows, int32_t n_q, int32_t dim, int32_t size,
+                       double decay, double eps, float* embed, float* enorm, float* codebook, float* cluster_size,
+                       float* embed_avg, void* workspace, void* stream);
+
+/*
  * Log-mel spectrogram and mel L1 distance: MelSpectrogram.forward and one resolution of MultiMelSpectrogramLoss.forward
  * (losses/mel_loss.py:19-156), with torch.stft's defaults as the reference calls it: center=True with reflect padding of n_fft/2
  * on each side, no normalisation, a one-sided spectrum of n_fft/2 + 1 bins, 1 + n_samples/hop frames.
