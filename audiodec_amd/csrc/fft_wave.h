@@ -58,4 +58,54 @@ __device__ __forceinline__ void wave_fft_bin(const float2* z, const float2* tw, 
     im = ey + (ox * w.y + oy * w.x);
 }
 
+// The transposes (vector-Jacobian products) of the two steps above, for the backward of a spectrum-domain loss.  Both are the
+// forward's linear maps transposed over the reals, with the forward's twiddles.
+
+// Transpose of wave_fft_bin, gathered: the gradient of DIF result Z[p], p < N (natural index; the caller stores it at p's
+// bit-reversed address), from the bin gradients g[k] = (d/d re, d/d im), k <= N.  Z[p] is operand A of bin p and operand B of bin
+// N - p; Z[0] is both operands of bins 0 and N.  Summed in that fixed order.
+template <int LOG2N>
+__device__ __forceinline__ float2 wave_fft_bin_t(const float2* g, const float2* tw, int p) {
+    constexpr int N = 1 << LOG2N;
+    float gx = 0.f, gy = 0.f;
+    auto add = [&](int k, bool as_a, bool as_b) {
+        const float2 gk = g[k], w = tw[k];
+        const float gox = gk.x * w.x + gk.y * w.y, goy = gk.y * w.x - gk.x * w.y;      // d/d ox, d/d oy
+        if (as_a) { gx += 0.5f * (gk.x - goy); gy += 0.5f * (gk.y + gox); }
+        if (as_b) { gx += 0.5f * (gk.x + goy); gy += 0.5f * (gox - gk.y); }
+    };
+    if (p == 0) {
+        add(0, true, true);
+        add(N, true, true);
+    } else {
+        add(p, true, false);
+        add(N - p, false, true);
+    }
+    return make_float2(gx, gy);
+}
+
+// Transpose of wave_fft_dif: the DIF stages in reverse order, each transposed -- (u, v) <- (a + conj(w) c, a - conj(w) c) with
+// the stage's own twiddle w -- which is a decimation-in-time FFT: bit-reversed order in, natural order out, in place.
+// The caller has synchronised after filling z; ends with a barrier.
+template <int LOG2N>
+__device__ __forceinline__ void wave_fft_dit_t(float2* z, const float2* tw) {
+    constexpr int N = 1 << LOG2N;
+    const int lane = threadIdx.x;
+#pragma unroll
+    for (int lh = 0; lh < LOG2N; ++lh) {
+        const int h = 1 << lh;
+#pragma unroll 4
+        for (int b = lane; b < N / 2; b += FFT_WAVE) {
+            const int pos = b & (h - 1);
+            const int i = ((b - pos) << 1) + pos;
+            const float2 a = z[i], c = z[i + h];
+            const float2 w = tw[pos << (LOG2N - lh)];
+            const float tx = c.x * w.x + c.y * w.y, ty = c.y * w.x - c.x * w.y;
+            z[i] = make_float2(a.x + tx, a.y + ty);
+            z[i + h] = make_float2(a.x - tx, a.y - ty);
+        }
+        __syncthreads();
+    }
+}
+
 }  // namespace adk

@@ -10,6 +10,11 @@
 //   logmel mode:   blocks of MEL_FB frames of one signal are staged in LDS, then stored as coalesced runs of (n_mels, frames)
 //   distance mode: |logmel(a) - logmel(b)| in f32, summed per lane in f64, never stored; per-workgroup f64 partials in a slab
 //                  and a fixed-order finalize launch (no float atomics), so the sum is bitwise reproducible run to run.
+// Backward (adk_logmel_vjp, adk_mel_distance_grad): the vector-Jacobian product of the above with respect to the signal.  A frame's
+// forward is recomputed (no spectra are saved), then walked back: log and clamp, the transposed mel projection (a sparse table per
+// bin), sqrt/clamp/power, the transposed untangle and FFT (fft_wave.h), the window.  The windowed frame gradients go to a slab
+// [n_signals][frames][n_fft]; a second launch gathers, per sample, its contributions through the reflect padding in ascending
+// frame order: no float atomics, so the gradient is bitwise reproducible too.
 #include "adk_common.h"
 #include "fft_wave.h"
 
@@ -46,9 +51,11 @@ __device__ __forceinline__ float clamp_min(float v, float eps) { return v < eps 
 
 // Log-mels of frame f of signal x into mels[i] = filter lane + 64 i.  buf: n_fft floats of LDS.  Ends with a barrier, so the
 // caller may reuse buf at once.
-template <int LOG2N>
+// KEEP (the backward's recompute): also keep[k] = (re, im) of bin k <= N and sums[i] = the unclamped mel sum of mels[i]; buf[k]
+// holds amp[k] on return.
+template <int LOG2N, bool KEEP = false>
 __device__ void frame_logmel(const float* __restrict__ x, long long f, const MelArgs& a, float* buf, const float2* tw,
-                             float (&mels)[MEL_MPL]) {
+                             float (&mels)[MEL_MPL], float2* keep = nullptr, float* sums = nullptr) {
     constexpr int NFFT = 2 << LOG2N, N = 1 << LOG2N, HALF = NFFT / 2;
     constexpr int PER = (N + 1 + MEL_THREADS - 1) / MEL_THREADS;
     const int lane = threadIdx.x;
@@ -77,6 +84,7 @@ __device__ void frame_logmel(const float* __restrict__ x, long long f, const Mel
             float re, im;
             wave_fft_bin<LOG2N>(z, tw, k, re, im);
             amp[q] = sqrtf(clamp_min(re * re + im * im, a.eps));
+            if constexpr (KEEP) keep[k] = make_float2(re, im);
         }
     }
     __syncthreads();
@@ -97,6 +105,7 @@ __device__ void frame_logmel(const float* __restrict__ x, long long f, const Mel
             for (int k = lo; k < hi; ++k) s = fmaf(a.fb_weight[off + (k - first)], buf[k], s);
         }
         mels[i] = mel_log(clamp_min(s, a.eps), a.log_base);
+        if constexpr (KEEP) sums[i] = s;
     }
     __syncthreads();
 }
@@ -183,6 +192,148 @@ __global__ __launch_bounds__(MEL_THREADS) void mel_distance_finalize_kernel(cons
     }
 }
 
+
+// ---- backward ----
+struct MelGradArgs {
+    const int* tb_range;                               // [n_fft/2 + 1][3]: first filter, filter count, offset into tb_weight
+    const float* tb_weight;
+    int n_tweights;
+};
+
+// The VJP of frame_logmel for the frame it just ran on with KEEP (buf[k] = amp, keep[k] = (re, im), sums): g[i] is the gradient
+// of log-mel lane + 64 i; out[j], j < n_fft, gets the windowed frame gradient.  gmel: MEL_MAX_MELS floats of LDS.  Ends with a
+// barrier.
+template <int LOG2N>
+__device__ void frame_logmel_vjp(const MelArgs& a, const MelGradArgs& ga, float* buf, const float2* tw, float2* keep, float* gmel,
+                                 const float (&sums)[MEL_MPL], const float (&g)[MEL_MPL], float* __restrict__ out) {
+    constexpr int NFFT = 2 << LOG2N, N = 1 << LOG2N;
+    constexpr int PER = (N + 1 + MEL_THREADS - 1) / MEL_THREADS;
+    const int lane = threadIdx.x;
+    // log and the second clamp: d log_b(mel) = 1 / (mel ln b); torch's clamp passes the gradient where mel >= eps
+    const float lnb = a.log_base == MEL_LOG_10 ? 2.302585092994046f : a.log_base == MEL_LOG_2 ? 0.6931471805599453f : 1.f;
+#pragma unroll
+    for (int i = 0; i < MEL_MPL; ++i) {
+        const int m = lane + i * MEL_THREADS;
+        if (m < a.n_mels) gmel[m] = sums[i] >= a.eps ? g[i] / (sums[i] * lnb) : 0.f;
+    }
+    __syncthreads();
+    // transposed mel projection in filter order, then sqrt / first clamp / power: (g_re, g_im) = g_amp (re, im) / amp
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+        const int k = lane + q * MEL_THREADS;
+        if (k <= N) {
+            const int first = ga.tb_range[3 * k], count = ga.tb_range[3 * k + 1], off = ga.tb_range[3 * k + 2];
+            const int lo = max(first, 0), hi = off < 0 ? lo : min(min(first + count, a.n_mels), ga.n_tweights - off + first);
+            float s = 0.f;
+            for (int m = lo; m < hi; ++m) s = fmaf(ga.tb_weight[off + (m - first)], gmel[m], s);
+            const float2 c = keep[k];
+            const float r = s / buf[k];
+            keep[k] = c.x * c.x + c.y * c.y >= a.eps ? make_float2(r * c.x, r * c.y) : make_float2(0.f, 0.f);
+        }
+    }
+    __syncthreads();
+    // transposed untangle into the bit-reversed addresses, then the transposed FFT: natural order out, float j = sample j
+    float2* z = reinterpret_cast<float2*>(buf);
+    for (int p = lane; p < N; p += MEL_THREADS)
+        z[__builtin_bitreverse32((unsigned)p) >> (32 - LOG2N)] = wave_fft_bin_t<LOG2N>(keep, tw, p);
+    __syncthreads();
+    wave_fft_dit_t<LOG2N>(z, tw);
+#pragma unroll 4
+    for (int j = lane; j < NFFT; j += MEL_THREADS) {
+        const int jw = j - a.lpad;
+        const float w = (jw >= 0 && jw < a.win_length) ? a.window[jw] : 0.f;
+        out[j] = __fmul_rn(buf[j], w);
+    }
+    __syncthreads();
+}
+
+// Windowed frame gradients of every frame into slab [n_signals][frames][n_fft].  DIST: the upstream gradient of a frame's log-mels
+// is sign(logmel(xa) - logmel(xb)) * (float)(scale * upstream[0]), the log-mels being the forward's own; else it is read from
+// g [n_signals][n_mels][frames].
+template <int LOG2N, bool DIST>
+__global__ __launch_bounds__(MEL_THREADS) void mel_grad_frames_kernel(const float* __restrict__ xa, const float* __restrict__ xb,
+                                                                      const float* __restrict__ g, double scale,
+                                                                      const float* __restrict__ upstream, int n_signals, MelArgs a,
+                                                                      MelGradArgs ga, float* __restrict__ slab) {
+    constexpr int NFFT = 2 << LOG2N, N = 1 << LOG2N;
+    extern __shared__ float lds[];
+    float2* tw = reinterpret_cast<float2*>(lds);                  // N + 1 twiddles
+    float* buf = lds + 2 * (N + 2);                              // NFFT floats
+    float2* keep = reinterpret_cast<float2*>(buf + NFFT);        // N + 1 bins
+    float* gmel = buf + NFFT + 2 * (N + 2);                      // MEL_MAX_MELS
+    build_twiddles<LOG2N>(tw);
+    __syncthreads();
+    const int lane = threadIdx.x;
+    const long long items = a.frames * n_signals;
+    float c = 0.f;
+    if constexpr (DIST) c = (float)(scale * (double)upstream[0]);
+    for (long long it = blockIdx.x; it < items; it += gridDim.x) {
+        const int s = (int)(it / a.frames);
+        const long long f = it - (long long)s * a.frames;
+        float ma[MEL_MPL], sums[MEL_MPL], gl[MEL_MPL];
+        if constexpr (DIST) {
+            float mb[MEL_MPL];
+            frame_logmel<LOG2N>(xb + (size_t)s * a.n_samples, f, a, buf, tw, mb);
+            frame_logmel<LOG2N, true>(xa + (size_t)s * a.n_samples, f, a, buf, tw, ma, keep, sums);
+#pragma unroll
+            for (int i = 0; i < MEL_MPL; ++i) {
+                const float d = __fsub_rn(ma[i], mb[i]);
+                gl[i] = d > 0.f ? c : d < 0.f ? -c : d;          // sign(0) = 0, NaN stays NaN
+            }
+        } else {
+            frame_logmel<LOG2N, true>(xa + (size_t)s * a.n_samples, f, a, buf, tw, ma, keep, sums);
+#pragma unroll
+            for (int i = 0; i < MEL_MPL; ++i) {
+                const int m = lane + i * MEL_THREADS;
+                gl[i] = m < a.n_mels ? g[((size_t)s * a.n_mels + m) * a.frames + f] : 0.f;
+            }
+        }
+        frame_logmel_vjp<LOG2N>(a, ga, buf, tw, keep, gmel, sums, gl, slab + (size_t)it * NFFT);
+    }
+}
+
+__device__ __forceinline__ long long floor_div(long long v, long long d) { return v >= 0 ? v / d : -((-v + d - 1) / d); }
+
+// The overlap-add through the reflect padding, gathered: sample t of a signal is padded position u = t, and also u = -t (t >= 1)
+// and u = 2 (T - 1) - t (t <= T - 2) where a frame reaches them; position u is float u - (f hop - n_fft/2) of frame f.  Frames in
+// ascending order, positions in ascending order within a frame; a sample no frame reaches gets 0.
+constexpr int MEL_GATHER_THREADS = 256;
+__global__ __launch_bounds__(MEL_GATHER_THREADS) void mel_grad_gather_kernel(const float* __restrict__ slab, int n_signals, int T,
+                                                                             int n_fft, int hop, long long frames,
+                                                                             float* __restrict__ grad_x) {
+    const long long total = (long long)n_signals * T, half = n_fft / 2;
+    for (long long e = (long long)blockIdx.x * MEL_GATHER_THREADS + threadIdx.x; e < total;
+         e += (long long)gridDim.x * MEL_GATHER_THREADS) {
+        const long long s = e / T, t = e - s * T;
+        const long long u[3] = {-t, t, 2LL * (T - 1) - t};
+        const bool on[3] = {t >= 1, true, t <= T - 2};
+        long long lo = frames, hi = -1;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            if (!on[i]) continue;
+            const long long f0 = max(floor_div(u[i] - half, hop) + 1, 0LL), f1 = min(floor_div(u[i] + half, hop), frames - 1);
+            if (f0 <= f1) { lo = min(lo, f0); hi = max(hi, f1); }
+        }
+        const float* fs = slab + (size_t)s * frames * n_fft;
+        float acc = 0.f;
+        for (long long f = lo; f <= hi; ++f) {
+            const long long base = f * hop - half;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                const long long j = u[i] - base;
+                if (on[i] && j >= 0 && j < n_fft) acc += fs[(size_t)f * n_fft + j];
+            }
+        }
+        grad_x[e] = acc;
+    }
+}
+
+template <int LOG2N>
+static size_t mel_grad_lds_bytes() {
+    constexpr int N = 1 << LOG2N;
+    return sizeof(float) * (2 * (N + 2) + 2 * N + 2 * (N + 2) + MEL_MAX_MELS);
+}
+
 template <int LOG2N>
 static size_t mel_lds_bytes(int n_mels, bool stage) {
     constexpr int N = 1 << LOG2N;
@@ -233,6 +384,57 @@ static void launch_distance(const float* xa, const float* xb, int n_signals, con
 }
 
 static int log2_of(int n) { int l = 0; while ((1 << l) < n) ++l; return l; }
+
+template <int LOG2N>
+static void launch_grad_frames(const float* xa, const float* xb, const float* g, double scale, const float* upstream, int n_signals,
+                               const MelArgs& a, const MelGradArgs& ga, float* slab, hipStream_t s) {
+    const int n_wg = mel_distance_workgroups(a.frames * n_signals);
+    if (xb)
+        hipLaunchKernelGGL((mel_grad_frames_kernel<LOG2N, true>), dim3(n_wg), dim3(MEL_THREADS), mel_grad_lds_bytes<LOG2N>(), s,
+                           xa, xb, g, scale, upstream, n_signals, a, ga, slab);
+    else
+        hipLaunchKernelGGL((mel_grad_frames_kernel<LOG2N, false>), dim3(n_wg), dim3(MEL_THREADS), mel_grad_lds_bytes<LOG2N>(), s,
+                           xa, xb, g, scale, upstream, n_signals, a, ga, slab);
+}
+
+// Both backward entry points: xb != nullptr is the distance gradient (scale, upstream), else the VJP of g.
+static int mel_grad(const char* fn, const float* xa, const float* xb, const float* g, double scale, const float* upstream,
+                    int n_signals, int n_samples, int n_fft, int hop, const float* window, int win_length, const int32_t* fb_range,
+                    const float* fb_weight, int n_weights, int n_mels, int log_base, float eps, const int32_t* tb_range,
+                    const float* tb_weight, int n_tweights, void* workspace, float* grad, void* stream) {
+    const std::string f(fn);
+    int rc = check_common(fn, n_signals, n_samples, n_fft, hop, window, win_length, fb_range, fb_weight, n_weights, n_mels, log_base);
+    if (rc != ADK_OK) return rc;
+    if (n_tweights <= 0) return fail(ADK_ERR_ARG, f + ": need n_tweights > 0");
+    if (!tb_range || !tb_weight) return fail(ADK_ERR_ARG, f + ": null pointer");
+    if (n_signals > 0 && (!xa || !(xb ? (const void*)upstream : (const void*)g) || !workspace || !grad))
+        return fail(ADK_ERR_ARG, f + ": null pointer");
+    if ((reinterpret_cast<uintptr_t>(xa) | reinterpret_cast<uintptr_t>(xb) | reinterpret_cast<uintptr_t>(g) |
+         reinterpret_cast<uintptr_t>(upstream) | reinterpret_cast<uintptr_t>(tb_range) | reinterpret_cast<uintptr_t>(tb_weight) |
+         reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(grad)) & 3)
+        return fail(ADK_ERR_ARG, f + ": every pointer must be 4-byte aligned");
+    if (n_signals == 0) return ADK_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DeviceGuard guard(device_of(grad));
+    const MelArgs a = make_args(n_samples, n_fft, hop, window, win_length, fb_range, fb_weight, n_weights, n_mels, log_base, eps);
+    MelGradArgs ga;
+    ga.tb_range = reinterpret_cast<const int*>(tb_range); ga.tb_weight = tb_weight; ga.n_tweights = n_tweights;
+    float* slab = static_cast<float*>(workspace);
+    switch (log2_of(n_fft) - 1) {
+        case 7: launch_grad_frames<7>(xa, xb, g, scale, upstream, n_signals, a, ga, slab, s); break;
+        case 8: launch_grad_frames<8>(xa, xb, g, scale, upstream, n_signals, a, ga, slab, s); break;
+        case 9: launch_grad_frames<9>(xa, xb, g, scale, upstream, n_signals, a, ga, slab, s); break;
+        case 10: launch_grad_frames<10>(xa, xb, g, scale, upstream, n_signals, a, ga, slab, s); break;
+        default: launch_grad_frames<11>(xa, xb, g, scale, upstream, n_signals, a, ga, slab, s); break;
+    }
+    ADK_HIP_CHECK(hipGetLastError());
+    const long long total = (long long)n_signals * n_samples;
+    const int n_wg = (int)std::min<long long>((total + MEL_GATHER_THREADS - 1) / MEL_GATHER_THREADS, 16 * MEL_MAX_WG);
+    hipLaunchKernelGGL(mel_grad_gather_kernel, dim3(n_wg), dim3(MEL_GATHER_THREADS), 0, s, slab, n_signals, n_samples, n_fft, hop,
+                       a.frames, grad);
+    ADK_HIP_CHECK(hipGetLastError());
+    return ADK_OK;
+}
 
 }  // namespace adk
 
@@ -303,4 +505,29 @@ extern "C" int adk_mel_distance(const float* a_sig, const float* b_sig, int32_t 
                        total * (long long)n_mels, sum, reinterpret_cast<long long*>(count), loss);
     ADK_HIP_CHECK(hipGetLastError());
     return ADK_OK;
+}
+
+extern "C" int64_t adk_mel_grad_workspace_bytes(int32_t n_signals, int32_t n_samples, int32_t n_fft, int32_t hop) {
+    if (n_signals < 0 || n_samples <= 0 || hop <= 0 || n_fft <= 0)
+        return fail(ADK_ERR_ARG, "adk_mel_grad_workspace_bytes: need n_signals >= 0, n_samples > 0, hop > 0, n_fft > 0");
+    return (int64_t)n_signals * mel_frames(n_samples, hop) * n_fft * (int64_t)sizeof(float);
+}
+
+extern "C" int adk_logmel_vjp(const float* x, const float* g, int32_t n_signals, int32_t n_samples, int32_t n_fft, int32_t hop,
+                              const float* window, int32_t win_length, const int32_t* fb_range, const float* fb_weight,
+                              int32_t n_weights, int32_t n_mels, int32_t log_base, float eps, const int32_t* tb_range,
+                              const float* tb_weight, int32_t n_tweights, void* workspace, float* grad_x, void* stream) {
+    return mel_grad("adk_logmel_vjp", x, nullptr, g, 0.0, nullptr, n_signals, n_samples, n_fft, hop, window, win_length, fb_range,
+                    fb_weight, n_weights, n_mels, log_base, eps, tb_range, tb_weight, n_tweights, workspace, grad_x, stream);
+}
+
+extern "C" int adk_mel_distance_grad(const float* a_sig, const float* b_sig, int32_t n_signals, int32_t n_samples, int32_t n_fft,
+                                     int32_t hop, const float* window, int32_t win_length, const int32_t* fb_range,
+                                     const float* fb_weight, int32_t n_weights, int32_t n_mels, int32_t log_base, float eps,
+                                     const int32_t* tb_range, const float* tb_weight, int32_t n_tweights, double scale,
+                                     const float* upstream, void* workspace, float* grad_a, void* stream) {
+    if (n_signals > 0 && !b_sig) return fail(ADK_ERR_ARG, "adk_mel_distance_grad: null pointer");
+    return mel_grad("adk_mel_distance_grad", a_sig, b_sig, nullptr, scale, upstream, n_signals, n_samples, n_fft, hop, window,
+                    win_length, fb_range, fb_weight, n_weights, n_mels, log_base, eps, tb_range, tb_weight, n_tweights, workspace,
+                    grad_a, stream);
 }

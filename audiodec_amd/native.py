@@ -73,6 +73,11 @@ SYMBOLS = {
     "adk_logmel": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, C.c_float, _vp, _vp]),
     "adk_mel_distance": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, C.c_float,
                                    _vp, _vp, _vp, _vp, _vp]),
+    "adk_mel_grad_workspace_bytes": (C.c_int64, [_i32, _i32, _i32, _i32]),
+    "adk_logmel_vjp": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, C.c_float,
+                                 _vp, _vp, _i32, _vp, _vp, _vp]),
+    "adk_mel_distance_grad": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, C.c_float,
+                                        _vp, _vp, _i32, C.c_double, _vp, _vp, _vp, _vp]),
     "adk_stft_workspace_bytes": (C.c_int64, [_i32, _i32, _i32, _i32]),
     "adk_stft_mag": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, C.c_float, _vp, _vp]),
     "adk_stft_distance": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),

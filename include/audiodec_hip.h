@@ -279,6 +279,35 @@ int adk_mel_distance(const float* a, const float* b, int32_t n_signals, int32_t 
                      void* stream);
 
 /*
+ * Mel-spectrogram loss, backward: the vector-Jacobian products of the two operations above with respect to the signal, as
+ * torch's autograd defines them for losses/mel_loss.py:84-94 (clamp passes the gradient where its input >= eps).  The arguments
+ * shared with adk_logmel mean the same; in addition the mel filters transposed, one contiguous filter range per bin:
+ *   tb_range    [n_fft/2 + 1][3] int32     bin k: first filter, filter count, offset of its weights in tb_weight
+ *   tb_weight   [n_tweights]               melmat[first .. first + count)[k], bin by bin, in filter order (inner zeros kept)
+ * adk_logmel_vjp: g [n_signals][n_mels][frames] f32 is the gradient of adk_logmel's out; grad_x [n_signals][n_samples] f32
+ * = sum over out of g d out / d x.  adk_mel_distance_grad: grad_a [n_signals][n_samples] = the gradient with respect to a of
+ * c sum |logmel(a) - logmel(b)|, c = (float)(scale * upstream[0]); upstream is a device pointer to one f32, read on the device.
+ * It is the same product with g = sign(logmel(a) - logmel(b)) c, the log-mels and their f32 difference being exactly those
+ * adk_mel_distance and adk_logmel compute, and sign(0) = 0.  For the mean over one resolution, scale = 1 / count.
+ * Each frame's forward is recomputed (no spectra are kept); its windowed gradient goes to workspace
+ * [n_signals][frames][n_fft] f32 = adk_mel_grad_workspace_bytes(n_signals, n_samples, n_fft, hop) bytes, 4-byte aligned, any
+ * contents; a second launch gathers every sample's contributions through the reflect padding in ascending frame order.  No float
+ * atomics: bitwise reproducible.  grad_x / grad_a is fully written (a sample no frame reaches gets 0).  n_signals == 0 is a
+ * no-op.  Same limits as adk_logmel; every argument is checked before any HIP call (ADK_ERR_ARG).  No allocation, no
+ * synchronisation.
+ */
+int64_t adk_mel_grad_workspace_bytes(int32_t n_signals, int32_t n_samples, int32_t n_fft, int32_t hop);
+int adk_logmel_vjp(const float* x, const float* g, int32_t n_signals, int32_t n_samples, int32_t n_fft, int32_t hop,
+                   const float* window, int32_t win_length, const int32_t* fb_range, const float* fb_weight, int32_t n_weights,
+                   int32_t n_mels, int32_t log_base, float eps, const int32_t* tb_range, const float* tb_weight,
+                   int32_t n_tweights, void* workspace, float* grad_x, void* stream);
+int adk_mel_distance_grad(const float* a, const float* b, int32_t n_signals, int32_t n_samples, int32_t n_fft, int32_t hop,
+                          const float* window, int32_t win_length, const int32_t* fb_range, const float* fb_weight,
+                          int32_t n_weights, int32_t n_mels, int32_t log_base, float eps, const int32_t* tb_range,
+                          const float* tb_weight, int32_t n_tweights, double scale, const float* upstream, void* workspace,
+                          float* grad_a, void* stream);
+
+/*
  * HiFi-GAN discriminator forward and its adversarial / feature-matching loss sums (models/vocoder/modules/discriminator.py:27-449,
  * losses/adversarial_loss.py, losses/feat_match_loss.py), exact f32 (the GEMM runs on the f32-input MFMA: a k-ordered fmaf chain).
  * adk_disc_conv: a non-causal, zero-padded, strided, grouped conv along H with bias and optional LeakyReLU:
