@@ -14,8 +14,9 @@
 //   disc_prep_kernel:   right-side reflect padding (the period discriminator's F.pad(x, (0, n_pad), "reflect")) and
 //                       AvgPool1d with count_include_pad (the scale discriminator's pooling between scales).
 //   disc_loss_kernel:   sum over a tensor of (x-1)^2, x^2, |a-b|, x, min(x-1, 0) or min(-x-1, 0) (f32 term, f64 sum) through
-//                       per-workgroup f64 partials and a fixed-order finalize launch: bitwise reproducible run to run.
+//                       per-workgroup f64 partials and a fixed-order finalize launch (reduce_f64.h): bitwise reproducible.
 #include "conv_gemm_f32.h"
+#include "reduce_f64.h"
 
 namespace adk {
 
@@ -142,7 +143,7 @@ __global__ __launch_bounds__(CG_THREADS) void disc_prep_kernel(const float* __re
 }
 
 static int disc_loss_workgroups(long long n) {
-    return (int)std::min<long long>(std::max<long long>((n + 4LL * CG_THREADS - 1) / (4LL * CG_THREADS), 1), DISC_LOSS_MAX_WG);
+    return capped_workgroups((n + 4LL * CG_THREADS - 1) / (4LL * CG_THREADS), DISC_LOSS_MAX_WG);
 }
 
 template <int KIND>
@@ -159,37 +160,10 @@ __device__ __forceinline__ double disc_term(const float* __restrict__ a, const f
 template <int KIND>
 __global__ __launch_bounds__(CG_THREADS) void disc_loss_kernel(const float* __restrict__ a, const float* __restrict__ b, long long n,
                                                                double* __restrict__ partial) {
-    __shared__ double wsum[CG_THREADS / 64];
-    double acc = 0.0;
+    double acc[1] = {0.0};
     for (long long i = (long long)blockIdx.x * CG_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * CG_THREADS)
-        acc += disc_term<KIND>(a, b, i);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = wsum[0];
-        for (int w = 1; w < CG_THREADS / 64; ++w) t += wsum[w];
-        partial[blockIdx.x] = t;
-    }
-}
-
-// One wave: folds the slab into sum (workgroups in a fixed order), adds count, writes loss = sum / count from the totals.
-__global__ __launch_bounds__(64) void disc_loss_finalize_kernel(const double* __restrict__ partial, int n_wg, long long n_values,
-                                                                double* __restrict__ sum, long long* __restrict__ count,
-                                                                float* __restrict__ loss) {
-    const int lane = threadIdx.x;
-    double t = 0.0;
-    for (int w = lane; w < n_wg; w += 64) t += partial[w];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) t += __shfl_xor(t, off, 64);
-    if (lane == 0) {
-        const double s = sum[0] + t;
-        const long long k = count[0] + n_values;
-        sum[0] = s;
-        count[0] = k;
-        if (loss) loss[0] = k > 0 ? (float)(s / (double)k) : __builtin_nanf("");
-    }
+        acc[0] += disc_term<KIND>(a, b, i);
+    workgroup_partials<1, CG_THREADS / 64>(acc, partial);
 }
 
 template <int WM, int WN, int TM, int TN>
@@ -286,12 +260,11 @@ extern "C" int adk_disc_loss(const float* a, const float* b, int64_t n, int32_t 
                              float* loss, void* stream) {
     if (n < 0) return fail(ADK_ERR_ARG, "adk_disc_loss: need n >= 0");
     if (kind < DISC_LOSS_MSE_ONE || kind > DISC_LOSS_HINGE_FAKE) return fail(ADK_ERR_ARG, "adk_disc_loss: kind must be 0..5");
-    if (!sum || !count) return fail(ADK_ERR_ARG, "adk_disc_loss: null accumulator pointer");
-    if (n > 0 && (!a || !workspace || (kind == DISC_LOSS_L1 && !b))) return fail(ADK_ERR_ARG, "adk_disc_loss: null pointer");
-    if ((reinterpret_cast<uintptr_t>(sum) | reinterpret_cast<uintptr_t>(count) | reinterpret_cast<uintptr_t>(workspace)) & 7)
-        return fail(ADK_ERR_ARG, "adk_disc_loss: sum/count/workspace must be 8-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(loss)) & 3)
-        return fail(ADK_ERR_ARG, "adk_disc_loss: a/b/loss must be 4-byte aligned");
+    const int rc = check_accumulators("adk_disc_loss", sum, count, workspace, n > 0, loss, nullptr);
+    if (rc != ADK_OK) return rc;
+    if (n > 0 && (!a || (kind == DISC_LOSS_L1 && !b))) return fail(ADK_ERR_ARG, "adk_disc_loss: null pointer");
+    if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 3)
+        return fail(ADK_ERR_ARG, "adk_disc_loss: a/b must be 4-byte aligned");
     if (n == 0 && !loss) return ADK_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
     DeviceGuard guard(device_of(sum));
@@ -308,8 +281,7 @@ extern "C" int adk_disc_loss(const float* a, const float* b, int64_t n, int32_t 
         }
         ADK_HIP_CHECK(hipGetLastError());
     }
-    hipLaunchKernelGGL(disc_loss_finalize_kernel, dim3(1), dim3(64), 0, s, partial, n_wg, (long long)n, sum,
-                       reinterpret_cast<long long*>(count), loss);
+    launch_distance_finalize<1>(partial, n_wg, (long long)n, sum, count, nullptr, loss, s);
     ADK_HIP_CHECK(hipGetLastError());
     return ADK_OK;
 }

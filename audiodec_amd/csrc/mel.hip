@@ -7,16 +7,17 @@
 // the bit reversal) plus the even/odd untangle.  Twiddles are exp(-2 pi i k / n_fft) evaluated in f64 and rounded to f32,
 // built once per workgroup.  The mel filters come from a sparse table (one contiguous bin range per filter), summed in bin
 // order.  A workgroup is one wave, so its barriers are wave-local; it loops over frames with no other synchronisation.
+// The frame load, the FFT and the clamped amplitudes are stft_frame.h's (shared with stft_loss.hip).
 //   logmel mode:   blocks of MEL_FB frames of one signal are staged in LDS, then stored as coalesced runs of (n_mels, frames)
 //   distance mode: |logmel(a) - logmel(b)| in f32, summed per lane in f64, never stored; per-workgroup f64 partials in a slab
-//                  and a fixed-order finalize launch (no float atomics), so the sum is bitwise reproducible run to run.
+//                  and a fixed-order finalize launch (reduce_f64.h; no float atomics), so the sum is bitwise reproducible.
 // Backward (adk_logmel_vjp, adk_mel_distance_grad): the vector-Jacobian product of the above with respect to the signal.  A frame's
 // forward is recomputed (no spectra are saved), then walked back: log and clamp, the transposed mel projection (a sparse table per
 // bin), sqrt/clamp/power, the transposed untangle and FFT (fft_wave.h), the window.  The windowed frame gradients go to a slab
 // [n_signals][frames][n_fft]; a second launch gathers, per sample, its contributions through the reflect padding in ascending
 // frame order: no float atomics, so the gradient is bitwise reproducible too.
-#include "adk_common.h"
-#include "fft_wave.h"
+#include "reduce_f64.h"
+#include "stft_frame.h"
 
 namespace adk {
 
@@ -27,27 +28,19 @@ constexpr int MEL_FB = 16;                             // logmel mode: frames pe
 constexpr int MEL_MAX_WG = 2048;
 constexpr int MEL_LOG_E = 0, MEL_LOG_2 = 2, MEL_LOG_10 = 10;
 
-static long long mel_frames(int n_samples, int hop) { return 1 + (long long)n_samples / hop; }
-
-static int mel_distance_workgroups(long long n_frames_total) {
-    return (int)std::min<long long>(std::max<long long>(n_frames_total, 1), MEL_MAX_WG);
-}
-
-struct MelArgs {
-    int n_samples, hop, win_length, lpad, n_mels, n_weights, log_base;
-    long long frames;
-    float eps;
-    const float* window;
+struct MelArgs : StftFrameArgs {
+    int n_mels, n_weights, log_base;
     const int* fb_range;                               // [n_mels][3]: first bin, bin count, offset into fb_weight
     const float* fb_weight;
+    MelArgs(int n_samples_, int n_fft, int hop_, const float* window_, int win_length_, const int32_t* fb_range_,
+            const float* fb_weight_, int n_weights_, int n_mels_, int log_base_, float eps_)
+        : StftFrameArgs(n_samples_, n_fft, hop_, window_, win_length_, eps_), n_mels(n_mels_), n_weights(n_weights_),
+          log_base(log_base_), fb_range(reinterpret_cast<const int*>(fb_range_)), fb_weight(fb_weight_) {}
 };
 
 __device__ __forceinline__ float mel_log(float v, int base) {
     return base == MEL_LOG_10 ? log10f(v) : base == MEL_LOG_2 ? log2f(v) : logf(v);
 }
-
-// clamp(v, min=eps) as torch.clamp: NaN stays NaN
-__device__ __forceinline__ float clamp_min(float v, float eps) { return v < eps ? eps : v; }
 
 // Log-mels of frame f of signal x into mels[i] = filter lane + 64 i.  buf: n_fft floats of LDS.  Ends with a barrier, so the
 // caller may reuse buf at once.
@@ -56,38 +49,11 @@ __device__ __forceinline__ float clamp_min(float v, float eps) { return v < eps 
 template <int LOG2N, bool KEEP = false>
 __device__ void frame_logmel(const float* __restrict__ x, long long f, const MelArgs& a, float* buf, const float2* tw,
                              float (&mels)[MEL_MPL], float2* keep = nullptr, float* sums = nullptr) {
-    constexpr int NFFT = 2 << LOG2N, N = 1 << LOG2N, HALF = NFFT / 2;
-    constexpr int PER = (N + 1 + MEL_THREADS - 1) / MEL_THREADS;
+    constexpr int N = 1 << LOG2N, PER = FRAME_PER<LOG2N>;
     const int lane = threadIdx.x;
-    const long long t0 = f * a.hop - HALF;
-    const int T = a.n_samples;
-    // load: reflect padding and the centred zero-padded window at load time; sample j is float j of the complex buffer
-#pragma unroll 4
-    for (int j = lane; j < NFFT; j += MEL_THREADS) {
-        long long t = t0 + j;
-        t = t < 0 ? -t : t;
-        t = t >= T ? 2LL * (T - 1) - t : t;
-        const int jw = j - a.lpad;
-        const float w = (jw >= 0 && jw < a.win_length) ? a.window[jw] : 0.f;
-        buf[j] = __fmul_rn(x[t], w);
-    }
-    __syncthreads();
-    float2* z = reinterpret_cast<float2*>(buf);
-    wave_fft_dif<LOG2N>(z, tw);                                  // fft_wave.h: radix-2 DIF, ends with a barrier
-    // untangle through the bit reversal (fft_wave.h)
     float amp[PER];
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-        const int k = lane + q * MEL_THREADS;
-        amp[q] = 0.f;
-        if (k <= N) {
-            float re, im;
-            wave_fft_bin<LOG2N>(z, tw, k, re, im);
-            amp[q] = sqrtf(clamp_min(re * re + im * im, a.eps));
-            if constexpr (KEEP) keep[k] = make_float2(re, im);
-        }
-    }
-    __syncthreads();
+    frame_spectrum<LOG2N>(x, f, a, buf, tw);
+    frame_amplitudes<LOG2N, KEEP>(buf, tw, a.eps, amp, keep);
 #pragma unroll
     for (int q = 0; q < PER; ++q) {
         const int k = lane + q * MEL_THREADS;
@@ -113,11 +79,10 @@ __device__ void frame_logmel(const float* __restrict__ x, long long f, const Mel
 template <int LOG2N>
 __global__ __launch_bounds__(MEL_THREADS) void logmel_kernel(const float* __restrict__ x, int n_signals, MelArgs a,
                                                              float* __restrict__ out) {
-    constexpr int NFFT = 2 << LOG2N, N = 1 << LOG2N;
     extern __shared__ float lds[];
-    float2* tw = reinterpret_cast<float2*>(lds);                  // N + 1 twiddles
-    float* buf = lds + 2 * (N + 2);                              // NFFT floats
-    float* stage = buf + NFFT;                                   // [n_mels][MEL_FB]
+    float2* tw = FrameLds<LOG2N>::tw(lds);
+    float* buf = FrameLds<LOG2N>::buf(lds);
+    float* stage = FrameLds<LOG2N>::extra(lds);                   // [n_mels][MEL_FB]
     build_twiddles<LOG2N>(tw);
     __syncthreads();
     const int lane = threadIdx.x;
@@ -150,10 +115,9 @@ __global__ __launch_bounds__(MEL_THREADS) void logmel_kernel(const float* __rest
 template <int LOG2N>
 __global__ __launch_bounds__(MEL_THREADS) void mel_distance_kernel(const float* __restrict__ xa, const float* __restrict__ xb,
                                                                    int n_signals, MelArgs a, double* __restrict__ partial) {
-    constexpr int N = 1 << LOG2N;
     extern __shared__ float lds[];
-    float2* tw = reinterpret_cast<float2*>(lds);
-    float* buf = lds + 2 * (N + 2);
+    float2* tw = FrameLds<LOG2N>::tw(lds);
+    float* buf = FrameLds<LOG2N>::buf(lds);
     build_twiddles<LOG2N>(tw);
     __syncthreads();
     const int lane = threadIdx.x;
@@ -169,29 +133,9 @@ __global__ __launch_bounds__(MEL_THREADS) void mel_distance_kernel(const float* 
         for (int i = 0; i < MEL_MPL; ++i)
             if (lane + i * MEL_THREADS < a.n_mels) acc += (double)fabsf(__fsub_rn(ma[i], mb[i]));
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    acc = wave_sum(acc);
     if (lane == 0) partial[blockIdx.x] = acc;
 }
-
-// One wave: folds the slab into sum (workgroups in a fixed order), adds count, writes loss from the totals.
-__global__ __launch_bounds__(MEL_THREADS) void mel_distance_finalize_kernel(const double* __restrict__ partial, int n_wg,
-                                                                            long long n_values, double* __restrict__ sum,
-                                                                            long long* __restrict__ count, float* __restrict__ loss) {
-    const int lane = threadIdx.x;
-    double t = 0.0;
-    for (int b = lane; b < n_wg; b += MEL_THREADS) t += partial[b];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) t += __shfl_xor(t, off, 64);
-    if (lane == 0) {
-        const double acc = sum[0] + t;
-        const long long n = count[0] + n_values;
-        sum[0] = acc;
-        count[0] = n;
-        if (loss) loss[0] = n > 0 ? (float)(acc / (double)n) : __builtin_nanf("");
-    }
-}
-
 
 // ---- backward ----
 struct MelGradArgs {
@@ -206,8 +150,7 @@ struct MelGradArgs {
 template <int LOG2N>
 __device__ void frame_logmel_vjp(const MelArgs& a, const MelGradArgs& ga, float* buf, const float2* tw, float2* keep, float* gmel,
                                  const float (&sums)[MEL_MPL], const float (&g)[MEL_MPL], float* __restrict__ out) {
-    constexpr int NFFT = 2 << LOG2N, N = 1 << LOG2N;
-    constexpr int PER = (N + 1 + MEL_THREADS - 1) / MEL_THREADS;
+    constexpr int NFFT = 2 << LOG2N, N = 1 << LOG2N, PER = FRAME_PER<LOG2N>;
     const int lane = threadIdx.x;
     // log and the second clamp: d log_b(mel) = 1 / (mel ln b); torch's clamp passes the gradient where mel >= eps
     const float lnb = a.log_base == MEL_LOG_10 ? 2.302585092994046f : a.log_base == MEL_LOG_2 ? 0.6931471805599453f : 1.f;
@@ -257,10 +200,10 @@ __global__ __launch_bounds__(MEL_THREADS) void mel_grad_frames_kernel(const floa
                                                                       MelGradArgs ga, float* __restrict__ slab) {
     constexpr int NFFT = 2 << LOG2N, N = 1 << LOG2N;
     extern __shared__ float lds[];
-    float2* tw = reinterpret_cast<float2*>(lds);                  // N + 1 twiddles
-    float* buf = lds + 2 * (N + 2);                              // NFFT floats
-    float2* keep = reinterpret_cast<float2*>(buf + NFFT);        // N + 1 bins
-    float* gmel = buf + NFFT + 2 * (N + 2);                      // MEL_MAX_MELS
+    float2* tw = FrameLds<LOG2N>::tw(lds);
+    float* buf = FrameLds<LOG2N>::buf(lds);
+    float2* keep = reinterpret_cast<float2*>(FrameLds<LOG2N>::extra(lds));    // N + 1 bins
+    float* gmel = FrameLds<LOG2N>::extra(lds) + 2 * (N + 2);     // MEL_MAX_MELS
     build_twiddles<LOG2N>(tw);
     __syncthreads();
     const int lane = threadIdx.x;
@@ -329,66 +272,40 @@ __global__ __launch_bounds__(MEL_GATHER_THREADS) void mel_grad_gather_kernel(con
 }
 
 template <int LOG2N>
-static size_t mel_grad_lds_bytes() {
-    constexpr int N = 1 << LOG2N;
-    return sizeof(float) * (2 * (N + 2) + 2 * N + 2 * (N + 2) + MEL_MAX_MELS);
-}
-
-template <int LOG2N>
-static size_t mel_lds_bytes(int n_mels, bool stage) {
-    constexpr int N = 1 << LOG2N;
-    return sizeof(float) * (2 * (N + 2) + 2 * N + (stage ? (size_t)n_mels * MEL_FB : 0));
-}
+static size_t mel_grad_lds_bytes() { return FrameLds<LOG2N>::bytes(2 * ((1 << LOG2N) + 2) + MEL_MAX_MELS); }
 
 static int check_common(const char* fn, int n_signals, int n_samples, int n_fft, int hop, const float* window, int win_length,
                         const int32_t* fb_range, const float* fb_weight, int n_weights, int n_mels, int log_base) {
     const std::string f(fn);
-    if (n_fft < 256 || n_fft > 4096 || (n_fft & (n_fft - 1)))
-        return fail(ADK_ERR_ARG, f + ": n_fft must be a power of two in [256, 4096]");
-    if (hop <= 0) return fail(ADK_ERR_ARG, f + ": need hop > 0");
-    if (win_length <= 0 || win_length > n_fft) return fail(ADK_ERR_ARG, f + ": need 0 < win_length <= n_fft");
-    if (n_signals < 0) return fail(ADK_ERR_ARG, f + ": need n_signals >= 0");
-    if (n_samples <= n_fft / 2)
-        return fail(ADK_ERR_ARG, f + ": reflect padding needs n_samples > n_fft / 2");
+    const int rc = check_stft_args(fn, n_signals, n_samples, n_fft, hop, window, win_length);
+    if (rc != ADK_OK) return rc;
     if (n_mels <= 0 || n_mels > MEL_MAX_MELS) return fail(ADK_ERR_ARG, f + ": need 0 < n_mels <= 256");
     if (n_weights <= 0) return fail(ADK_ERR_ARG, f + ": need n_weights > 0");
     if (log_base != MEL_LOG_E && log_base != MEL_LOG_2 && log_base != MEL_LOG_10)
         return fail(ADK_ERR_ARG, f + ": log_base must be 0 (natural), 2 or 10");
-    if (!window || !fb_range || !fb_weight) return fail(ADK_ERR_ARG, f + ": null pointer");
-    if ((reinterpret_cast<uintptr_t>(window) | reinterpret_cast<uintptr_t>(fb_range) | reinterpret_cast<uintptr_t>(fb_weight)) & 3)
-        return fail(ADK_ERR_ARG, f + ": window/fb_range/fb_weight must be 4-byte aligned");
+    if (!fb_range || !fb_weight) return fail(ADK_ERR_ARG, f + ": null pointer");
+    if ((reinterpret_cast<uintptr_t>(fb_range) | reinterpret_cast<uintptr_t>(fb_weight)) & 3)
+        return fail(ADK_ERR_ARG, f + ": fb_range/fb_weight must be 4-byte aligned");
     return ADK_OK;
-}
-
-static MelArgs make_args(int n_samples, int n_fft, int hop, const float* window, int win_length, const int32_t* fb_range,
-                         const float* fb_weight, int n_weights, int n_mels, int log_base, float eps) {
-    MelArgs a;
-    a.n_samples = n_samples; a.hop = hop; a.win_length = win_length; a.lpad = (n_fft - win_length) / 2;
-    a.n_mels = n_mels; a.n_weights = n_weights; a.log_base = log_base;
-    a.frames = mel_frames(n_samples, hop); a.eps = eps;
-    a.window = window; a.fb_range = reinterpret_cast<const int*>(fb_range); a.fb_weight = fb_weight;
-    return a;
 }
 
 template <int LOG2N>
 static void launch_logmel(const float* x, int n_signals, const MelArgs& a, float* out, hipStream_t s) {
     const long long items = (a.frames + MEL_FB - 1) / MEL_FB * n_signals;
     const int n_wg = (int)std::min<long long>(items, 4 * MEL_MAX_WG);
-    hipLaunchKernelGGL(logmel_kernel<LOG2N>, dim3(n_wg), dim3(MEL_THREADS), mel_lds_bytes<LOG2N>(a.n_mels, true), s, x, n_signals, a, out);
+    hipLaunchKernelGGL(logmel_kernel<LOG2N>, dim3(n_wg), dim3(MEL_THREADS), FrameLds<LOG2N>::bytes((size_t)a.n_mels * MEL_FB), s, x, n_signals, a, out);
 }
 
 template <int LOG2N>
 static void launch_distance(const float* xa, const float* xb, int n_signals, const MelArgs& a, int n_wg, double* partial, hipStream_t s) {
-    hipLaunchKernelGGL(mel_distance_kernel<LOG2N>, dim3(n_wg), dim3(MEL_THREADS), mel_lds_bytes<LOG2N>(a.n_mels, false), s,
+    hipLaunchKernelGGL(mel_distance_kernel<LOG2N>, dim3(n_wg), dim3(MEL_THREADS), FrameLds<LOG2N>::bytes(), s,
                        xa, xb, n_signals, a, partial);
 }
-
-static int log2_of(int n) { int l = 0; while ((1 << l) < n) ++l; return l; }
 
 template <int LOG2N>
 static void launch_grad_frames(const float* xa, const float* xb, const float* g, double scale, const float* upstream, int n_signals,
                                const MelArgs& a, const MelGradArgs& ga, float* slab, hipStream_t s) {
-    const int n_wg = mel_distance_workgroups(a.frames * n_signals);
+    const int n_wg = capped_workgroups(a.frames * n_signals, MEL_MAX_WG);
     if (xb)
         hipLaunchKernelGGL((mel_grad_frames_kernel<LOG2N, true>), dim3(n_wg), dim3(MEL_THREADS), mel_grad_lds_bytes<LOG2N>(), s,
                            xa, xb, g, scale, upstream, n_signals, a, ga, slab);
@@ -416,17 +333,13 @@ static int mel_grad(const char* fn, const float* xa, const float* xb, const floa
     if (n_signals == 0) return ADK_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
     DeviceGuard guard(device_of(grad));
-    const MelArgs a = make_args(n_samples, n_fft, hop, window, win_length, fb_range, fb_weight, n_weights, n_mels, log_base, eps);
+    const MelArgs a(n_samples, n_fft, hop, window, win_length, fb_range, fb_weight, n_weights, n_mels, log_base, eps);
     MelGradArgs ga;
     ga.tb_range = reinterpret_cast<const int*>(tb_range); ga.tb_weight = tb_weight; ga.n_tweights = n_tweights;
     float* slab = static_cast<float*>(workspace);
-    switch (log2_of(n_fft) - 1) {
-        case 7: launch_grad_frames<7>(xa, xb, g, scale, upstream, n_signals, a, ga, slab, s); break;
-        case 8: launch_grad_frames<8>(xa, xb, g, scale, upstream, n_signals, a, ga, slab, s); break;
-        case 9: launch_grad_frames<9>(xa, xb, g, scale, upstream, n_signals, a, ga, slab, s); break;
-        case 10: launch_grad_frames<10>(xa, xb, g, scale, upstream, n_signals, a, ga, slab, s); break;
-        default: launch_grad_frames<11>(xa, xb, g, scale, upstream, n_signals, a, ga, slab, s); break;
-    }
+    dispatch_log2n(n_fft, [&](auto L) {
+        launch_grad_frames<decltype(L)::value>(xa, xb, g, scale, upstream, n_signals, a, ga, slab, s);
+    });
     ADK_HIP_CHECK(hipGetLastError());
     const long long total = (long long)n_signals * n_samples;
     const int n_wg = (int)std::min<long long>((total + MEL_GATHER_THREADS - 1) / MEL_GATHER_THREADS, 16 * MEL_MAX_WG);
@@ -444,7 +357,7 @@ extern "C" int64_t adk_mel_workspace_bytes(int32_t n_signals, int32_t n_samples,
     if (n_signals < 0 || n_samples <= 0 || hop <= 0 || n_fft <= 0)
         return fail(ADK_ERR_ARG, "adk_mel_workspace_bytes: need n_signals >= 0, n_samples > 0, hop > 0, n_fft > 0");
     if (n_signals == 0) return 0;
-    return (int64_t)mel_distance_workgroups(mel_frames(n_samples, hop) * n_signals) * (int64_t)sizeof(double);
+    return (int64_t)capped_workgroups(stft_frames(n_samples, hop) * n_signals, MEL_MAX_WG) * (int64_t)sizeof(double);
 }
 
 extern "C" int adk_logmel(const float* x, int32_t n_signals, int32_t n_samples, int32_t n_fft, int32_t hop, const float* window,
@@ -459,14 +372,8 @@ extern "C" int adk_logmel(const float* x, int32_t n_signals, int32_t n_samples, 
     if (n_signals == 0) return ADK_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
     DeviceGuard guard(device_of(out));
-    const MelArgs a = make_args(n_samples, n_fft, hop, window, win_length, fb_range, fb_weight, n_weights, n_mels, log_base, eps);
-    switch (log2_of(n_fft) - 1) {
-        case 7: launch_logmel<7>(x, n_signals, a, out, s); break;
-        case 8: launch_logmel<8>(x, n_signals, a, out, s); break;
-        case 9: launch_logmel<9>(x, n_signals, a, out, s); break;
-        case 10: launch_logmel<10>(x, n_signals, a, out, s); break;
-        default: launch_logmel<11>(x, n_signals, a, out, s); break;
-    }
+    const MelArgs a(n_samples, n_fft, hop, window, win_length, fb_range, fb_weight, n_weights, n_mels, log_base, eps);
+    dispatch_log2n(n_fft, [&](auto L) { launch_logmel<decltype(L)::value>(x, n_signals, a, out, s); });
     ADK_HIP_CHECK(hipGetLastError());
     return ADK_OK;
 }
@@ -478,31 +385,23 @@ extern "C" int adk_mel_distance(const float* a_sig, const float* b_sig, int32_t 
     int rc = check_common("adk_mel_distance", n_signals, n_samples, n_fft, hop, window, win_length, fb_range, fb_weight,
                           n_weights, n_mels, log_base);
     if (rc != ADK_OK) return rc;
-    if (!sum || !count) return fail(ADK_ERR_ARG, "adk_mel_distance: null accumulator pointer");
-    if (n_signals > 0 && (!a_sig || !b_sig || !workspace)) return fail(ADK_ERR_ARG, "adk_mel_distance: null pointer");
-    if ((reinterpret_cast<uintptr_t>(sum) | reinterpret_cast<uintptr_t>(count) | reinterpret_cast<uintptr_t>(workspace)) & 7)
-        return fail(ADK_ERR_ARG, "adk_mel_distance: sum/count/workspace must be 8-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(a_sig) | reinterpret_cast<uintptr_t>(b_sig) | reinterpret_cast<uintptr_t>(loss)) & 3)
-        return fail(ADK_ERR_ARG, "adk_mel_distance: a/b/loss must be 4-byte aligned");
+    rc = check_accumulators("adk_mel_distance", sum, count, workspace, n_signals > 0, loss, nullptr);
+    if (rc != ADK_OK) return rc;
+    if (n_signals > 0 && (!a_sig || !b_sig)) return fail(ADK_ERR_ARG, "adk_mel_distance: null pointer");
+    if ((reinterpret_cast<uintptr_t>(a_sig) | reinterpret_cast<uintptr_t>(b_sig)) & 3)
+        return fail(ADK_ERR_ARG, "adk_mel_distance: a/b must be 4-byte aligned");
     if (n_signals == 0 && !loss) return ADK_OK;        // nothing to fold, nothing asked for
     hipStream_t s = static_cast<hipStream_t>(stream);
     DeviceGuard guard(device_of(sum));
-    const MelArgs a = make_args(n_samples, n_fft, hop, window, win_length, fb_range, fb_weight, n_weights, n_mels, log_base, eps);
+    const MelArgs a(n_samples, n_fft, hop, window, win_length, fb_range, fb_weight, n_weights, n_mels, log_base, eps);
     const long long total = a.frames * n_signals;
-    const int n_wg = n_signals > 0 ? mel_distance_workgroups(total) : 0;
+    const int n_wg = n_signals > 0 ? capped_workgroups(total, MEL_MAX_WG) : 0;
     double* partial = static_cast<double*>(workspace);
     if (n_signals > 0) {
-        switch (log2_of(n_fft) - 1) {
-            case 7: launch_distance<7>(a_sig, b_sig, n_signals, a, n_wg, partial, s); break;
-            case 8: launch_distance<8>(a_sig, b_sig, n_signals, a, n_wg, partial, s); break;
-            case 9: launch_distance<9>(a_sig, b_sig, n_signals, a, n_wg, partial, s); break;
-            case 10: launch_distance<10>(a_sig, b_sig, n_signals, a, n_wg, partial, s); break;
-            default: launch_distance<11>(a_sig, b_sig, n_signals, a, n_wg, partial, s); break;
-        }
+        dispatch_log2n(n_fft, [&](auto L) { launch_distance<decltype(L)::value>(a_sig, b_sig, n_signals, a, n_wg, partial, s); });
         ADK_HIP_CHECK(hipGetLastError());
     }
-    hipLaunchKernelGGL(mel_distance_finalize_kernel, dim3(1), dim3(MEL_THREADS), 0, s, partial, n_wg,
-                       total * (long long)n_mels, sum, reinterpret_cast<long long*>(count), loss);
+    launch_distance_finalize<1>(partial, n_wg, total * (long long)n_mels, sum, count, nullptr, loss, s);
     ADK_HIP_CHECK(hipGetLastError());
     return ADK_OK;
 }
@@ -510,7 +409,7 @@ extern "C" int adk_mel_distance(const float* a_sig, const float* b_sig, int32_t 
 extern "C" int64_t adk_mel_grad_workspace_bytes(int32_t n_signals, int32_t n_samples, int32_t n_fft, int32_t hop) {
     if (n_signals < 0 || n_samples <= 0 || hop <= 0 || n_fft <= 0)
         return fail(ADK_ERR_ARG, "adk_mel_grad_workspace_bytes: need n_signals >= 0, n_samples > 0, hop > 0, n_fft > 0");
-    return (int64_t)n_signals * mel_frames(n_samples, hop) * n_fft * (int64_t)sizeof(float);
+    return (int64_t)n_signals * stft_frames(n_samples, hop) * n_fft * (int64_t)sizeof(float);
 }
 
 extern "C" int adk_logmel_vjp(const float* x, const float* g, int32_t n_signals, int32_t n_samples, int32_t n_fft, int32_t hop,

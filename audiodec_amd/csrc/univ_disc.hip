@@ -6,7 +6,8 @@
 //                        frame f of signal s = xp[f*hop - n_fft/2 + j] (reflected at both ends of xp) * window_centred[j], where
 //                        xp is x with `pad` zeros on both sides (never materialised: both paddings and the window are applied
 //                        while loading); out [s][f][k] = |X_f[k]|, k <= n_fft/2, no eps clamp.  One frame per wave, the FFT of
-//                        fft_wave.h (shared with mel.hip); a frame's bins are one coalesced run of the output.
+//                        fft_wave.h; a frame's bins are one coalesced run of the output.  The load loop is this kernel's own and not
+//                        stft_frame.h's: it zero-pads inside the reflect padding and writes a literal 0 outside the window.
 //   conv2d_gemm_kernel:  x [n][c_in][H][W] -> y [n][c_out][H'][W'], kernel (kh, kw), stride (sh, sw), zero padding (ph, pw) by
 //                        predicated loads, as an implicit GEMM through conv_gemm_f32.h's core:
 //                          Y[m][n] = bias[m] + sum_kk W[kk][m] X[kk][n],  m < c_out,  kk = (ci*kh + th)*kw + tw,
@@ -15,7 +16,7 @@
 //   conv2d_direct_kernel: one thread per output position and block of COB output channels, for the c_in = 1 first layer and
 //                        the c_out = 1 output layer, where a GEMM tile would be mostly padding.  Same k order.
 #include "conv_gemm_f32.h"
-#include "fft_wave.h"
+#include "stft_frame.h"
 
 namespace adk {
 
@@ -188,8 +189,6 @@ static void launch_conv2d_gemm(const Conv2dArgs& c, hipStream_t s) {
     hipLaunchKernelGGL((conv2d_gemm_kernel<WM, WN, TM, TN>), grid, dim3(CG_THREADS), tab, s, c);
 }
 
-static int ud_log2(int n) { int l = 0; while ((1 << l) < n) ++l; return l; }
-
 }  // namespace adk
 
 using namespace adk;
@@ -201,10 +200,8 @@ extern "C" int64_t adk_spectrogram_frames(int32_t n_samples, int32_t pad, int32_
 
 extern "C" int adk_spectrogram(const float* x, int32_t n_signals, int32_t n_samples, int32_t pad, int32_t n_fft, int32_t hop,
                                const float* window, int32_t win_length, float* out, void* stream) {
-    if (n_fft < 256 || n_fft > 4096 || (n_fft & (n_fft - 1)))
-        return fail(ADK_ERR_ARG, "adk_spectrogram: n_fft must be a power of two in [256, 4096]");
-    if (hop <= 0) return fail(ADK_ERR_ARG, "adk_spectrogram: need hop > 0");
-    if (win_length <= 0 || win_length > n_fft) return fail(ADK_ERR_ARG, "adk_spectrogram: need 0 < win_length <= n_fft");
+    const int rc = check_fft_sizes("adk_spectrogram", n_fft, hop, win_length);
+    if (rc != ADK_OK) return rc;
     if (n_signals < 0 || n_samples <= 0 || pad < 0) return fail(ADK_ERR_ARG, "adk_spectrogram: need n_signals >= 0, n_samples > 0, pad >= 0");
     if ((long long)n_samples + 2LL * pad <= n_fft / 2)
         return fail(ADK_ERR_ARG, "adk_spectrogram: reflect padding needs n_samples + 2 pad > n_fft / 2");
@@ -220,13 +217,7 @@ extern "C" int adk_spectrogram(const float* x, int32_t n_signals, int32_t n_samp
     a.window = window;
     hipStream_t s = static_cast<hipStream_t>(stream);
     DeviceGuard guard(device_of(out));
-    switch (ud_log2(n_fft) - 1) {
-        case 7: launch_spec<7>(x, n_signals, a, out, s); break;
-        case 8: launch_spec<8>(x, n_signals, a, out, s); break;
-        case 9: launch_spec<9>(x, n_signals, a, out, s); break;
-        case 10: launch_spec<10>(x, n_signals, a, out, s); break;
-        default: launch_spec<11>(x, n_signals, a, out, s); break;
-    }
+    dispatch_log2n(n_fft, [&](auto L) { launch_spec<decltype(L)::value>(x, n_signals, a, out, s); });
     ADK_HIP_CHECK(hipGetLastError());
     return ADK_OK;
 }

@@ -15,13 +15,14 @@ Forward only by default: an input that requires grad while grad is enabled raise
 recomputed and walked back on the device, and the frame gradients are overlap-added in a fixed order, so the gradient is
 bitwise reproducible like the value.  The backward is once-differentiable.
 """
-import ctypes as C
 import math
 
 import numpy as np
 import torch
 
 from . import lazy_guard, native
+from .loss_common import (_Accumulator, _check_fft_size, _check_length, _mean_f32, _no_grad_inputs, _ptr, _settled, _signals,
+                          _workspace, num_frames)
 
 _LOG_BASES = {None: 0, 2.0: 2, 10.0: 10}
 
@@ -78,28 +79,6 @@ def transposed_filters(melmat):
     return sparse_filters(np.ascontiguousarray(np.asarray(melmat, np.float32).T))
 
 
-def num_frames(n_samples, hop_size):
-    """Frames of torch.stft(center=True): 1 + T // hop."""
-    return 1 + int(n_samples) // int(hop_size)
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _settled(t):
-    lg = lazy_guard.log_of(t)
-    if lg is not None:
-        lg.settle()
-    return lazy_guard.plain(t)
-
-
-def _no_grad_inputs(*ts):
-    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in ts):
-        raise NotImplementedError("the HIP metric losses (mel, STFT, shape) are forward only: run them under torch.no_grad() or "
-                                  "detach the inputs")
-
-
 def _wants_grad(differentiable, x):
     return bool(differentiable) and torch.is_grad_enabled() and isinstance(x, torch.Tensor) and x.requires_grad
 
@@ -153,15 +132,6 @@ class _MelLossFn(torch.autograd.Function):
         return grad.reshape(shape).to(device=device, dtype=dtype), None, None, None
 
 
-def _signals(x, device):
-    """(B, T) or (B, C, T) -> contiguous float32 (B*C, T) on `device` (MelSpectrogram.forward's reshape)."""
-    if x.dim() == 3:
-        x = x.reshape(-1, x.size(2))
-    if x.dim() != 2:
-        raise ValueError(f"expected a (B, T) or (B, C, T) waveform, got shape {tuple(x.shape)}")
-    return x.to(device=device, dtype=torch.float32).contiguous()
-
-
 class MelSpectrogram:
     """losses/mel_loss.py:19-94 on the HIP path.  Same arguments and defaults.
 
@@ -186,8 +156,7 @@ class MelSpectrogram:
         if window != "hann_window":
             raise NotImplementedError(f"window {window!r}: only 'hann_window' is implemented on the HIP path")
         n = self.fft_size
-        if n < 256 or n > 4096 or n & (n - 1):
-            raise NotImplementedError(f"fft_size {n}: the HIP path implements powers of two from 256 to 4096")
+        _check_fft_size(n)
         if self.hop_size <= 0 or not 0 < self.win_length <= n:
             raise ValueError(f"need hop_size > 0 and 0 < win_length <= fft_size, got {self.hop_size}, {self.win_length}")
         self.num_mels = int(num_mels)
@@ -224,9 +193,7 @@ class MelSpectrogram:
         return num_frames(n_samples, self.hop_size)
 
     def check_length(self, n_samples):
-        if n_samples <= self.fft_size // 2:
-            raise ValueError(f"input length {n_samples}: reflect padding of fft_size // 2 = {self.fft_size // 2} needs more "
-                             f"than {self.fft_size // 2} samples (torch.stft raises for it too)")
+        _check_length(n_samples, self.fft_size)
 
     def _args(self):
         return (self.fft_size, self.hop_size, _ptr(self._window_d), self.win_length, _ptr(self._range_d), _ptr(self._weights_d),
@@ -267,10 +234,7 @@ class MelSpectrogram:
         dev = self._dev
         n, T = (int(y.shape[0]), int(y.shape[1])) if y is not None else (0, self.fft_size)
         lib = native.lib()
-        ws_bytes = int(lib.adk_mel_workspace_bytes(n, T, self.fft_size, self.hop_size))
-        if ws_bytes < 0:
-            native.check(ws_bytes, "adk_mel_workspace_bytes")
-        ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.float64, device=dev) if ws_bytes else None
+        ws = _workspace(int(lib.adk_mel_workspace_bytes(n, T, self.fft_size, self.hop_size)), "adk_mel_workspace_bytes", dev)
         n_fft, hop, win, wl, rng, wts, nw, nm, lb, eps = self._args()
         native.check(lib.adk_mel_distance(_ptr(y_hat), _ptr(y), n, T, n_fft, hop, win, wl, rng, wts, nw, nm, lb, eps,
                                           _ptr(sum_), _ptr(count), _ptr(ws), _ptr(loss), native.current_stream(dev)),
@@ -356,17 +320,12 @@ class MultiMelSpectrogramLoss:
         losses = torch.empty(R, dtype=torch.float32, device=dev)
         for r, f in enumerate(self.mel_transfers):
             f.fold(a, b, sums[r:r + 1], counts[r:r + 1], losses[r:r + 1])
-        if R == 1:
-            return losses[0]
-        mel_loss = losses[0]
-        for r in range(1, R):                       # mel_loss += l1 per resolution, then / R, in f32 as the reference
-            mel_loss = mel_loss + losses[r]
-        return mel_loss / R
+        return _mean_f32(losses)
 
     __call__ = forward
 
 
-class MelDistance:
+class MelDistance(_Accumulator):
     """The mel-spectrogram loss of a config's ``mel_loss_params``, accumulated on the device over any number of batches.
 
     ``update(y_hat, y)`` folds the per-resolution L1 sums and element counts without synchronising (lazy-guard results are
@@ -377,14 +336,7 @@ class MelDistance:
     def __init__(self, loss_params, device):
         self.loss = MultiMelSpectrogramLoss(**dict(loss_params), device=device)
         self.device = self.loss.device
-        R = len(self.loss.mel_transfers)
-        self._sum = torch.zeros(R, dtype=torch.float64, device=self.device)
-        self._count = torch.zeros(R, dtype=torch.int64, device=self.device)
-
-    def reset(self):
-        self._sum.zero_()
-        self._count.zero_()
-        return self
+        self._init_totals(len(self.loss.mel_transfers), self.device)
 
     def update(self, y_hat, y):
         a, b = self.loss.prepare(y_hat, y)
@@ -393,15 +345,6 @@ class MelDistance:
         for r, f in enumerate(self.loss.mel_transfers):
             f.fold(a, b, self._sum[r:r + 1], self._count[r:r + 1])
         return self
-
-    def count(self):
-        return [int(c) for c in self._count.cpu()]
-
-    def value(self):
-        s, c = self._sum.cpu().numpy(), self._count.cpu().numpy()
-        if (c == 0).any():
-            return float("nan")
-        return float(np.mean(s / c))
 
 
 def from_config(config, device=None, differentiable=False):

@@ -16,29 +16,8 @@ import numpy as np
 import torch
 
 from . import native
-from .mel import _no_grad_inputs, _ptr, _settled, _signals, num_frames
-
-
-def _check_fft_size(n):
-    if n < 256 or n > 4096 or n & (n - 1):
-        raise NotImplementedError(f"fft_size {n}: the HIP path implements powers of two from 256 to 4096")
-
-
-def _check_length(n_samples, fft_size):
-    if n_samples <= fft_size // 2:
-        raise ValueError(f"input length {n_samples}: reflect padding of fft_size // 2 = {fft_size // 2} needs more than "
-                         f"{fft_size // 2} samples (torch.stft raises for it too)")
-
-
-def _workspace(n_bytes, what, dev):
-    if n_bytes < 0:
-        native.check(n_bytes, what)
-    return torch.empty((n_bytes + 7) // 8, dtype=torch.float64, device=dev) if n_bytes else None
-
-
-def _device_of(x):
-    dev = x.device if x.device.type == "cuda" else torch.device("cuda", torch.cuda.current_device())
-    return native.require_gpu(dev)
+from .loss_common import (_check_fft_size, _check_length, _device_of, _mean_f32, _no_grad_inputs, _ptr, _settled, _signals,
+                          _workspace, num_frames)
 
 
 def stft(x, fft_size, hop_size, win_length, window, eps=1e-7):
@@ -203,10 +182,7 @@ class MultiResolutionSTFTLoss:
         res = torch.empty(R, 2, dtype=torch.float32, device=dev)
         for r, f in enumerate(self.stft_losses):
             f.fold(a, b, sums[r], counts[r:r + 1], res[r, 0:1], res[r, 1:2])
-        sc_loss, mag_loss = res[0, 0], res[0, 1]
-        for r in range(1, R):                       # += per resolution, then / R, in f32 as the reference
-            sc_loss, mag_loss = sc_loss + res[r, 0], mag_loss + res[r, 1]
-        return sc_loss / R, mag_loss / R
+        return _mean_f32(res[:, 0]), _mean_f32(res[:, 1])
 
     __call__ = forward
 

@@ -7,12 +7,10 @@ tail is dropped -- and ``MultiWindowShapeLoss`` (41-75) its mean over window len
 
 Forward only: an input that requires grad while grad is enabled raises NotImplementedError.
 """
-import numpy as np
 import torch
 
 from . import native
-from .mel import _no_grad_inputs, _ptr, _settled, _signals
-from .stft_loss import _device_of, _workspace
+from .loss_common import _Accumulator, _device_of, _mean_f32, _no_grad_inputs, _ptr, _settled, _signals, _workspace
 
 
 def num_windows(n_samples, winlen):
@@ -80,15 +78,12 @@ class MultiWindowShapeLoss:
         losses = torch.empty(R, dtype=torch.float32, device=b.device)
         for r, f in enumerate(self.shape_losses):
             f.fold(a, b, sums[r:r + 1], counts[r:r + 1], losses[r:r + 1])
-        loss = losses[0]
-        for r in range(1, R):                       # += per window length, then / R, in f32 as the reference
-            loss = loss + losses[r]
-        return loss / R
+        return _mean_f32(losses)
 
     __call__ = forward
 
 
-class ShapeDistance:
+class ShapeDistance(_Accumulator):
     """The shape loss of a config's ``shape_loss_params``, accumulated on the device over any number of batches.
 
     ``update(y_hat, y)`` folds the per-window-length sums and window counts without synchronising.  ``value()`` is the mean over
@@ -98,14 +93,7 @@ class ShapeDistance:
     def __init__(self, loss_params, device):
         self.loss = MultiWindowShapeLoss(**dict(loss_params))
         self.device = native.require_gpu(torch.device(device))
-        R = len(self.loss.shape_losses)
-        self._sum = torch.zeros(R, dtype=torch.float64, device=self.device)
-        self._count = torch.zeros(R, dtype=torch.int64, device=self.device)
-
-    def reset(self):
-        self._sum.zero_()
-        self._count.zero_()
-        return self
+        self._init_totals(len(self.loss.shape_losses), self.device)
 
     def update(self, y_hat, y):
         a, b = self.loss.prepare(y_hat, y)
@@ -115,15 +103,6 @@ class ShapeDistance:
         for r, f in enumerate(self.loss.shape_losses):
             f.fold(a, b, self._sum[r:r + 1], self._count[r:r + 1])
         return self
-
-    def count(self):
-        return [int(c) for c in self._count.cpu()]
-
-    def value(self):
-        s, c = self._sum.cpu().numpy(), self._count.cpu().numpy()
-        if (c == 0).any():
-            return float("nan")
-        return float(np.mean(s / c))
 
 
 def from_config(config, device=None):
