@@ -13,11 +13,11 @@
 //                  and a fixed-order finalize launch (reduce_f64.h; no float atomics), so the sum is bitwise reproducible.
 // Backward (adk_logmel_vjp, adk_mel_distance_grad): the vector-Jacobian product of the above with respect to the signal.  A frame's
 // forward is recomputed (no spectra are saved), then walked back: log and clamp, the transposed mel projection (a sparse table per
-// bin), sqrt/clamp/power, the transposed untangle and FFT (fft_wave.h), the window.  The windowed frame gradients go to a slab
-// [n_signals][frames][n_fft]; a second launch gathers, per sample, its contributions through the reflect padding in ascending
-// frame order: no float atomics, so the gradient is bitwise reproducible too.
+// bin), sqrt/clamp/power, then stft_grad.h's tail (shared with stft_loss.hip): the transposed untangle and FFT, the window.  The
+// windowed frame gradients go to a slab [n_signals][frames][n_fft]; a second launch gathers, per sample, its contributions through
+// the reflect padding in ascending frame order: no float atomics, so the gradient is bitwise reproducible too.
 #include "reduce_f64.h"
-#include "stft_frame.h"
+#include "stft_grad.h"
 
 namespace adk {
 
@@ -150,7 +150,7 @@ struct MelGradArgs {
 template <int LOG2N>
 __device__ void frame_logmel_vjp(const MelArgs& a, const MelGradArgs& ga, float* buf, const float2* tw, float2* keep, float* gmel,
                                  const float (&sums)[MEL_MPL], const float (&g)[MEL_MPL], float* __restrict__ out) {
-    constexpr int NFFT = 2 << LOG2N, N = 1 << LOG2N, PER = FRAME_PER<LOG2N>;
+    constexpr int N = 1 << LOG2N, PER = FRAME_PER<LOG2N>;
     const int lane = threadIdx.x;
     // log and the second clamp: d log_b(mel) = 1 / (mel ln b); torch's clamp passes the gradient where mel >= eps
     const float lnb = a.log_base == MEL_LOG_10 ? 2.302585092994046f : a.log_base == MEL_LOG_2 ? 0.6931471805599453f : 1.f;
@@ -175,19 +175,7 @@ __device__ void frame_logmel_vjp(const MelArgs& a, const MelGradArgs& ga, float*
         }
     }
     __syncthreads();
-    // transposed untangle into the bit-reversed addresses, then the transposed FFT: natural order out, float j = sample j
-    float2* z = reinterpret_cast<float2*>(buf);
-    for (int p = lane; p < N; p += MEL_THREADS)
-        z[__builtin_bitreverse32((unsigned)p) >> (32 - LOG2N)] = wave_fft_bin_t<LOG2N>(keep, tw, p);
-    __syncthreads();
-    wave_fft_dit_t<LOG2N>(z, tw);
-#pragma unroll 4
-    for (int j = lane; j < NFFT; j += MEL_THREADS) {
-        const int jw = j - a.lpad;
-        const float w = (jw >= 0 && jw < a.win_length) ? a.window[jw] : 0.f;
-        out[j] = __fmul_rn(buf[j], w);
-    }
-    __syncthreads();
+    frame_grad_tail<LOG2N>(a, buf, tw, keep, out);
 }
 
 // Windowed frame gradients of every frame into slab [n_signals][frames][n_fft].  DIST: the upstream gradient of a frame's log-mels
@@ -232,42 +220,6 @@ __global__ __launch_bounds__(MEL_THREADS) void mel_grad_frames_kernel(const floa
             }
         }
         frame_logmel_vjp<LOG2N>(a, ga, buf, tw, keep, gmel, sums, gl, slab + (size_t)it * NFFT);
-    }
-}
-
-__device__ __forceinline__ long long floor_div(long long v, long long d) { return v >= 0 ? v / d : -((-v + d - 1) / d); }
-
-// The overlap-add through the reflect padding, gathered: sample t of a signal is padded position u = t, and also u = -t (t >= 1)
-// and u = 2 (T - 1) - t (t <= T - 2) where a frame reaches them; position u is float u - (f hop - n_fft/2) of frame f.  Frames in
-// ascending order, positions in ascending order within a frame; a sample no frame reaches gets 0.
-constexpr int MEL_GATHER_THREADS = 256;
-__global__ __launch_bounds__(MEL_GATHER_THREADS) void mel_grad_gather_kernel(const float* __restrict__ slab, int n_signals, int T,
-                                                                             int n_fft, int hop, long long frames,
-                                                                             float* __restrict__ grad_x) {
-    const long long total = (long long)n_signals * T, half = n_fft / 2;
-    for (long long e = (long long)blockIdx.x * MEL_GATHER_THREADS + threadIdx.x; e < total;
-         e += (long long)gridDim.x * MEL_GATHER_THREADS) {
-        const long long s = e / T, t = e - s * T;
-        const long long u[3] = {-t, t, 2LL * (T - 1) - t};
-        const bool on[3] = {t >= 1, true, t <= T - 2};
-        long long lo = frames, hi = -1;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            if (!on[i]) continue;
-            const long long f0 = max(floor_div(u[i] - half, hop) + 1, 0LL), f1 = min(floor_div(u[i] + half, hop), frames - 1);
-            if (f0 <= f1) { lo = min(lo, f0); hi = max(hi, f1); }
-        }
-        const float* fs = slab + (size_t)s * frames * n_fft;
-        float acc = 0.f;
-        for (long long f = lo; f <= hi; ++f) {
-            const long long base = f * hop - half;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                const long long j = u[i] - base;
-                if (on[i] && j >= 0 && j < n_fft) acc += fs[(size_t)f * n_fft + j];
-            }
-        }
-        grad_x[e] = acc;
     }
 }
 
@@ -341,10 +293,7 @@ static int mel_grad(const char* fn, const float* xa, const float* xb, const floa
         launch_grad_frames<decltype(L)::value>(xa, xb, g, scale, upstream, n_signals, a, ga, slab, s);
     });
     ADK_HIP_CHECK(hipGetLastError());
-    const long long total = (long long)n_signals * n_samples;
-    const int n_wg = (int)std::min<long long>((total + MEL_GATHER_THREADS - 1) / MEL_GATHER_THREADS, 16 * MEL_MAX_WG);
-    hipLaunchKernelGGL(mel_grad_gather_kernel, dim3(n_wg), dim3(MEL_GATHER_THREADS), 0, s, slab, n_signals, n_samples, n_fft, hop,
-                       a.frames, grad);
+    launch_frame_grad_gather(slab, n_signals, n_samples, n_fft, hop, a.frames, grad, s);
     ADK_HIP_CHECK(hipGetLastError());
     return ADK_OK;
 }

@@ -13,8 +13,14 @@
 //   shape distance: max |.| over windows of winlen samples of y_hat and of y, sum |a - b| (f32 difference, f64 sum)
 // Every sum goes through reduce_f64.h: per-workgroup f64 partials in a caller-supplied slab (the workgroup count is a function
 // of the shape only) and a one-wave finalize that folds them in a fixed order: no float atomics, bitwise reproducible run to run.
+// Backward (adk_grad_stft_mag, adk_grad_stft_distance, adk_grad_shape_distance), with respect to the predicted signal only.  A
+// frame's forward is recomputed by the same core, so the (re, im) walked back are the forward's own bits; the per-bin gradient of
+// the magnitude becomes (g_re, g_im) = g (re, im) / mag where re^2 + im^2 >= eps, then stft_grad.h's tail (shared with mel.hip)
+// and its gather.  The distance gradient reads the forward's folded sums and the upstream gradients from device memory: no host
+// synchronisation.  The shape gradient puts one value at the first maximum of each window; windows are disjoint, so every
+// sample is stored once.  No float atomics anywhere: bitwise reproducible.
 #include "reduce_f64.h"
-#include "stft_frame.h"
+#include "stft_grad.h"
 
 namespace adk {
 
@@ -140,6 +146,134 @@ __global__ __launch_bounds__(RED_THREADS) void shape_distance_kernel(const float
     workgroup_partials<1>(acc, partial);
 }
 
+// ---- backward ----
+
+__device__ __forceinline__ float sign_or_nan(float d) { return d > 0.f ? 1.f : d < 0.f ? -1.f : d; }   // sign(0) = 0, NaN stays NaN
+
+// Windowed frame gradients of every frame into slab [n_signals][frames][n_fft]: the loop of stft_distance_kernel.  The gradient gX
+// of magnitude bin k of the x frame is, DIST: c_sc (xm - ym) - c_mag sgn / xm with sgn the sign of the forward's own term
+// log_rounded(ym) - log_rounded(xm), c_sc = scale_sc up_sc[0] / sqrt(S0 S1) (0 where S0 == 0: torch's norm backward at 0) and
+// c_mag = scale_mag up_mag[0], both in f64 from device memory and rounded to f32, (S0, S1) = sums[0..1] as adk_stft_distance left
+// them; else it is read from g [n_signals][frames][n_fft/2 + 1].
+template <int LOG2N, bool DIST>
+__global__ __launch_bounds__(STFT_THREADS) void stft_grad_frames_kernel(const float* __restrict__ x, const float* __restrict__ y,
+                                                                        const float* __restrict__ g, const double* __restrict__ sums,
+                                                                        double scale_sc, const float* __restrict__ up_sc,
+                                                                        double scale_mag, const float* __restrict__ up_mag,
+                                                                        int n_signals, StftFrameArgs a, float* __restrict__ slab) {
+    constexpr int NFFT = 2 << LOG2N, N = 1 << LOG2N, PER = FRAME_PER<LOG2N>;
+    extern __shared__ float lds[];
+    float2* tw = FrameLds<LOG2N>::tw(lds);
+    float* buf = FrameLds<LOG2N>::buf(lds);
+    float2* keep = reinterpret_cast<float2*>(FrameLds<LOG2N>::extra(lds));    // N + 1 bins
+    build_twiddles<LOG2N>(tw);
+    __syncthreads();
+    const int lane = threadIdx.x;
+    float c_sc = 0.f, c_mag = 0.f;
+    if constexpr (DIST) {
+        const double s0 = sums[0], s1 = sums[1];
+        c_sc = s0 == 0.0 ? 0.f : (float)(scale_sc * (double)up_sc[0] / sqrt(s0 * s1));
+        c_mag = (float)(scale_mag * (double)up_mag[0]);
+    }
+    const long long items = a.frames * n_signals;
+    for (long long it = blockIdx.x; it < items; it += gridDim.x) {
+        const long long s = it / a.frames, f = it - s * a.frames;
+        float xm[PER], gx[PER];
+        if constexpr (DIST) {
+            float ym[PER];
+            frame_spectrum<LOG2N>(y + (size_t)s * a.n_samples, f, a, buf, tw);
+            frame_amplitudes<LOG2N>(buf, tw, a.eps, ym);
+            frame_spectrum<LOG2N>(x + (size_t)s * a.n_samples, f, a, buf, tw);
+            frame_amplitudes<LOG2N, true>(buf, tw, a.eps, xm, keep);
+#pragma unroll
+            for (int q = 0; q < PER; ++q) {
+                gx[q] = 0.f;
+                if (lane + q * STFT_THREADS <= N) {
+                    const float sgn = sign_or_nan(__fsub_rn(log_rounded(ym[q]), log_rounded(xm[q])));
+                    gx[q] = c_sc * __fsub_rn(xm[q], ym[q]) - c_mag * sgn / xm[q];
+                }
+            }
+        } else {
+            frame_spectrum<LOG2N>(x + (size_t)s * a.n_samples, f, a, buf, tw);
+            frame_amplitudes<LOG2N, true>(buf, tw, a.eps, xm, keep);
+            const float* gs = g + (size_t)it * (N + 1);
+#pragma unroll
+            for (int q = 0; q < PER; ++q) {
+                const int k = lane + q * STFT_THREADS;
+                gx[q] = k <= N ? gs[k] : 0.f;
+            }
+        }
+        // sqrt / clamp / power: (g_re, g_im) = gX (re, im) / mag; torch's clamp passes the gradient where re^2 + im^2 >= eps
+#pragma unroll
+        for (int q = 0; q < PER; ++q) {
+            const int k = lane + q * STFT_THREADS;
+            if (k <= N) {
+                const float2 c = keep[k];
+                const float r = gx[q] / xm[q];
+                keep[k] = c.x * c.x + c.y * c.y >= a.eps ? make_float2(r * c.x, r * c.y) : make_float2(0.f, 0.f);
+            }
+        }
+        __syncthreads();
+        frame_grad_tail<LOG2N>(a, buf, tw, keep, slab + (size_t)it * NFFT);
+    }
+}
+
+// The backward of shape_distance_kernel, in its two forms.  Per window: a = max |y_hat| and its FIRST index (what MaxPool1d's
+// backward selects; the wave form reduces (value, index) pairs, a tie going to the lower index), b = max |y|;
+// grad[index] = sign(a - b) sign(y_hat[index]) c, every other sample of the window and the dropped tail get 0.
+template <bool WAVE>
+__global__ __launch_bounds__(RED_THREADS) void shape_grad_kernel(const float* __restrict__ y_hat, const float* __restrict__ y,
+                                                                int n_signals, int n_samples, int winlen, double scale,
+                                                                const float* __restrict__ upstream, float* __restrict__ grad) {
+    const long long windows = n_samples / winlen, items = windows * n_signals;
+    const float c = (float)(scale * (double)upstream[0]);
+    if constexpr (WAVE) {
+        const int lane = threadIdx.x & 63;
+        for (long long it = (long long)blockIdx.x * RED_WAVES + (threadIdx.x >> 6); it < items; it += (long long)gridDim.x * RED_WAVES) {
+            const long long s = it / windows, w = it - s * windows;
+            const size_t base = (size_t)s * n_samples + (size_t)w * winlen;
+            float ma = 0.f, mb = 0.f;
+            int idx = lane < winlen ? lane : 0;
+            for (int j = lane; j < winlen; j += 64) {
+                const float v = fabsf(y_hat[base + j]);
+                if (v > ma || v != v) { ma = v; idx = j; }
+                mb = nan_max(mb, fabsf(y[base + j]));
+            }
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) {
+                const float ov = __shfl_xor(ma, off, 64);
+                const int oi = __shfl_xor(idx, off, 64);
+                if (ov > ma || (ov != ov && ma == ma) || (ov == ma && oi < idx)) { ma = ov; idx = oi; }
+                mb = nan_max(mb, __shfl_xor(mb, off, 64));
+            }
+            ma = __shfl(ma, 0, 64);
+            idx = __shfl(idx, 0, 64);
+            const float v = sign_or_nan(__fsub_rn(ma, mb)) * sign_or_nan(y_hat[base + idx]) * c;
+            for (int j = lane; j < winlen; j += 64) grad[base + j] = j == idx ? v : 0.f;
+        }
+    } else {
+        for (long long it = (long long)blockIdx.x * RED_THREADS + threadIdx.x; it < items; it += (long long)gridDim.x * RED_THREADS) {
+            const long long s = it / windows, w = it - s * windows;
+            const size_t base = (size_t)s * n_samples + (size_t)w * winlen;
+            float ma = 0.f, mb = 0.f;
+            int idx = 0;
+            for (int j = 0; j < winlen; ++j) {
+                const float v = fabsf(y_hat[base + j]);
+                if (v > ma || v != v) { ma = v; idx = j; }
+                mb = nan_max(mb, fabsf(y[base + j]));
+            }
+            const float v = sign_or_nan(__fsub_rn(ma, mb)) * sign_or_nan(y_hat[base + idx]) * c;
+            for (int j = 0; j < winlen; ++j) grad[base + j] = j == idx ? v : 0.f;
+        }
+    }
+    // the tail MaxPool1d drops
+    const long long tail = n_samples - windows * winlen, tails = tail * n_signals;
+    for (long long e = (long long)blockIdx.x * RED_THREADS + threadIdx.x; e < tails; e += (long long)gridDim.x * RED_THREADS) {
+        const long long s = e / tail, r = e - s * tail;
+        grad[(size_t)s * n_samples + (size_t)(windows * winlen + r)] = 0.f;
+    }
+}
+
 template <int LOG2N>
 static void launch_stft_mag(const float* x, int n_signals, const StftFrameArgs& a, float* out, hipStream_t s) {
     const int n_wg = (int)std::min<long long>(a.frames * n_signals, 4 * STFT_MAX_WG);
@@ -161,6 +295,50 @@ static int shape_workgroups(int n_signals, int n_samples, int winlen) {
     const long long items = (long long)(n_samples / winlen) * n_signals;
     const int per_wg = winlen >= SHAPE_WAVE_WINLEN ? RED_WAVES : RED_THREADS;
     return capped_workgroups((items + per_wg - 1) / per_wg, STFT_MAX_WG);
+}
+
+template <int LOG2N>
+static size_t stft_grad_lds_bytes() { return FrameLds<LOG2N>::bytes(2 * ((1 << LOG2N) + 2)); }
+
+template <int LOG2N>
+static void launch_stft_grad_frames(const float* x, const float* y, const float* g, const double* sums, double scale_sc,
+                                    const float* up_sc, double scale_mag, const float* up_mag, int n_signals, const StftFrameArgs& a,
+                                    float* slab, hipStream_t s) {
+    const int n_wg = capped_workgroups(a.frames * n_signals, STFT_MAX_WG);
+    if (y)
+        hipLaunchKernelGGL((stft_grad_frames_kernel<LOG2N, true>), dim3(n_wg), dim3(STFT_THREADS), stft_grad_lds_bytes<LOG2N>(), s,
+                           x, y, g, sums, scale_sc, up_sc, scale_mag, up_mag, n_signals, a, slab);
+    else
+        hipLaunchKernelGGL((stft_grad_frames_kernel<LOG2N, false>), dim3(n_wg), dim3(STFT_THREADS), stft_grad_lds_bytes<LOG2N>(), s,
+                           x, y, g, sums, scale_sc, up_sc, scale_mag, up_mag, n_signals, a, slab);
+}
+
+// Both STFT backward entry points: dist is the distance gradient (y, sums, scales, upstreams), else the VJP of g.
+static int stft_grad(const char* fn, bool dist, const float* x, const float* y, const float* g, const double* sums, double scale_sc,
+                     const float* up_sc, double scale_mag, const float* up_mag, int n_signals, int n_samples, int n_fft, int hop,
+                     const float* window, int win_length, float eps, void* workspace, float* grad, void* stream) {
+    const std::string f(fn);
+    const int rc = check_stft_args(fn, n_signals, n_samples, n_fft, hop, window, win_length);
+    if (rc != ADK_OK) return rc;
+    const bool given = dist ? (y && sums && up_sc && up_mag) : g != nullptr;
+    if (n_signals > 0 && (!x || !given || !workspace || !grad)) return fail(ADK_ERR_ARG, f + ": null pointer");
+    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(g) |
+         reinterpret_cast<uintptr_t>(up_sc) | reinterpret_cast<uintptr_t>(up_mag) | reinterpret_cast<uintptr_t>(workspace) |
+         reinterpret_cast<uintptr_t>(grad)) & 3)
+        return fail(ADK_ERR_ARG, f + ": every pointer must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(sums) & 7) return fail(ADK_ERR_ARG, f + ": sums must be 8-byte aligned");
+    if (n_signals == 0) return ADK_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DeviceGuard guard(device_of(grad));
+    const StftFrameArgs a(n_samples, n_fft, hop, window, win_length, eps);
+    float* slab = static_cast<float*>(workspace);
+    dispatch_log2n(n_fft, [&](auto L) {
+        launch_stft_grad_frames<decltype(L)::value>(x, dist ? y : nullptr, g, sums, scale_sc, up_sc, scale_mag, up_mag, n_signals, a, slab, s);
+    });
+    ADK_HIP_CHECK(hipGetLastError());
+    launch_frame_grad_gather(slab, n_signals, n_samples, n_fft, hop, a.frames, grad, s);
+    ADK_HIP_CHECK(hipGetLastError());
+    return ADK_OK;
 }
 
 }  // namespace adk
@@ -281,6 +459,46 @@ extern "C" int adk_shape_distance(const float* y_hat, const float* y, int32_t n_
         ADK_HIP_CHECK(hipGetLastError());
     }
     launch_distance_finalize<1>(partial, n_wg, (long long)(n_samples / winlen) * n_signals, sum, count, nullptr, loss, s);
+    ADK_HIP_CHECK(hipGetLastError());
+    return ADK_OK;
+}
+
+extern "C" int64_t adk_grad_stft_workspace_bytes(int32_t n_signals, int32_t n_samples, int32_t n_fft, int32_t hop) {
+    if (n_signals < 0 || n_samples <= 0 || hop <= 0 || n_fft <= 0)
+        return fail(ADK_ERR_ARG, "adk_grad_stft_workspace_bytes: need n_signals >= 0, n_samples > 0, hop > 0, n_fft > 0");
+    return (int64_t)n_signals * stft_frames(n_samples, hop) * n_fft * (int64_t)sizeof(float);
+}
+
+extern "C" int adk_grad_stft_mag(const float* x, const float* g, int32_t n_signals, int32_t n_samples, int32_t n_fft, int32_t hop,
+                                const float* window, int32_t win_length, float eps, void* workspace, float* grad_x, void* stream) {
+    return stft_grad("adk_grad_stft_mag", false, x, nullptr, g, nullptr, 0.0, nullptr, 0.0, nullptr, n_signals, n_samples, n_fft, hop, window,
+                     win_length, eps, workspace, grad_x, stream);
+}
+
+extern "C" int adk_grad_stft_distance(const float* x, const float* y, int32_t n_signals, int32_t n_samples, int32_t n_fft,
+                                      int32_t hop, const float* window, int32_t win_length, float eps, const double* sums,
+                                      double scale_sc, const float* up_sc, double scale_mag, const float* up_mag, void* workspace,
+                                      float* grad_x, void* stream) {
+    return stft_grad("adk_grad_stft_distance", true, x, y, nullptr, sums, scale_sc, up_sc, scale_mag, up_mag, n_signals, n_samples, n_fft,
+                     hop, window, win_length, eps, workspace, grad_x, stream);
+}
+
+extern "C" int adk_grad_shape_distance(const float* y_hat, const float* y, int32_t n_signals, int32_t n_samples, int32_t winlen,
+                                       double scale, const float* upstream, float* grad, void* stream) {
+    int rc = check_shape("adk_grad_shape_distance", n_signals, n_samples, winlen);
+    if (rc != ADK_OK) return rc;
+    if (n_signals > 0 && (!y_hat || !y || !upstream || !grad)) return fail(ADK_ERR_ARG, "adk_grad_shape_distance: null pointer");
+    if ((reinterpret_cast<uintptr_t>(y_hat) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(upstream) |
+         reinterpret_cast<uintptr_t>(grad)) & 3)
+        return fail(ADK_ERR_ARG, "adk_grad_shape_distance: every pointer must be 4-byte aligned");
+    if (n_signals == 0) return ADK_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DeviceGuard guard(device_of(grad));
+    const int n_wg = shape_workgroups(n_signals, n_samples, winlen);
+    if (winlen >= SHAPE_WAVE_WINLEN)
+        hipLaunchKernelGGL(shape_grad_kernel<true>, dim3(n_wg), dim3(RED_THREADS), 0, s, y_hat, y, n_signals, n_samples, winlen, scale, upstream, grad);
+    else
+        hipLaunchKernelGGL(shape_grad_kernel<false>, dim3(n_wg), dim3(RED_THREADS), 0, s, y_hat, y, n_signals, n_samples, winlen, scale, upstream, grad);
     ADK_HIP_CHECK(hipGetLastError());
     return ADK_OK;
 }

@@ -30,6 +30,10 @@ def _no_grad_inputs(*ts):
                                   "detach the inputs")
 
 
+def _wants_grad(differentiable, x):
+    return bool(differentiable) and torch.is_grad_enabled() and isinstance(x, torch.Tensor) and x.requires_grad
+
+
 def _signals(x, device):
     """(B, T) or (B, C, T) -> contiguous float32 (B*C, T) on `device` (MelSpectrogram.forward's reshape)."""
     if x.dim() == 3:

@@ -22,7 +22,7 @@ import torch
 
 from . import lazy_guard, native
 from .loss_common import (_Accumulator, _check_fft_size, _check_length, _mean_f32, _no_grad_inputs, _ptr, _settled, _signals,
-                          _workspace, num_frames)
+                          _wants_grad, _workspace, num_frames)
 
 _LOG_BASES = {None: 0, 2.0: 2, 10.0: 10}
 
@@ -77,10 +77,6 @@ def transposed_filters(melmat):
     """(n_mels, bins) -> (range int32 [bins][3] = first filter, count, offset; weights float32): sparse_filters of melmat.T, one
     contiguous filter range per bin, for the backward's g_amp[k] = sum_m melmat[m][k] g_mel[m]."""
     return sparse_filters(np.ascontiguousarray(np.asarray(melmat, np.float32).T))
-
-
-def _wants_grad(differentiable, x):
-    return bool(differentiable) and torch.is_grad_enabled() and isinstance(x, torch.Tensor) and x.requires_grad
 
 
 def _grad_workspace(n, T, n_fft, hop, dev):

@@ -85,6 +85,11 @@ SYMBOLS = {
     "adk_mag_distance": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "adk_shape_workspace_bytes": (C.c_int64, [_i32, _i32, _i32]),
     "adk_shape_distance": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "adk_grad_stft_workspace_bytes": (C.c_int64, [_i32, _i32, _i32, _i32]),
+    "adk_grad_stft_mag": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, C.c_float, _vp, _vp, _vp]),
+    "adk_grad_stft_distance": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, C.c_float, _vp, C.c_double, _vp,
+                                         C.c_double, _vp, _vp, _vp, _vp]),
+    "adk_grad_shape_distance": (C.c_int, [_vp, _vp, _i32, _i32, _i32, C.c_double, _vp, _vp, _vp]),
     "adk_disc_conv": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float, _i32, _vp]),
     "adk_disc_prep": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "adk_disc_loss_workspace_bytes": (C.c_int64, [_i64]),

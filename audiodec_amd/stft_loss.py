@@ -1,4 +1,5 @@
-"""Multi-resolution STFT loss on the device (adk_stft_mag, adk_stft_distance, adk_mag_distance).
+"""Multi-resolution STFT loss on the device (adk_stft_mag, adk_stft_distance, adk_mag_distance) and its backward
+(adk_grad_stft_mag, adk_grad_stft_distance).
 
 Mirrors ``losses/stft_loss.py``: ``stft`` (lines 19-35), ``SpectralConvergenceLoss``, ``LogSTFTMagnitudeLoss``, ``STFTLoss``
 (38-117) and ``MultiResolutionSTFTLoss`` (120-170), which the reference's trainers build from ``config['stft_loss_params']``
@@ -10,22 +11,130 @@ Each resolution runs one HIP kernel that frames both signals with reflect paddin
 two terms need into an f64 accumulator on the device, without ever writing a magnitude.  The window is
 ``getattr(torch, window)(win_length)``: any torch window function, the kernel takes its values.
 
-Forward only: an input that requires grad while grad is enabled raises NotImplementedError.
+Forward only by default: an input that requires grad while grad is enabled raises NotImplementedError.  Built (``stft``: called)
+with ``differentiable=True``, ``stft``, ``STFTLoss`` and ``MultiResolutionSTFTLoss`` give the predicted signal ``x`` -- never the
+target ``y`` -- a gradient through ``torch.autograd``: each frame's forward is recomputed and walked back on the device, the two
+terms' upstream gradients and the forward's folded sums are read there (no host synchronisation), and the frame gradients are
+overlap-added in a fixed order, so the gradient is bitwise reproducible like the value.  The backward is once-differentiable.
+``SpectralConvergenceLoss`` / ``LogSTFTMagnitudeLoss`` on given magnitude tensors and ``STFTDistance`` stay forward only.
 """
 import numpy as np
 import torch
 
-from . import native
+from . import lazy_guard, native
 from .loss_common import (_check_fft_size, _check_length, _device_of, _mean_f32, _no_grad_inputs, _ptr, _settled, _signals,
-                          _workspace, num_frames)
+                          _wants_grad, _workspace, num_frames)
 
 
-def stft(x, fft_size, hop_size, win_length, window, eps=1e-7):
+def _grad_workspace(n, T, n_fft, hop, dev):
+    ws_bytes = int(native.lib().adk_grad_stft_workspace_bytes(n, T, n_fft, hop))
+    if ws_bytes < 0:
+        native.check(ws_bytes, "adk_grad_stft_workspace_bytes")
+    return torch.empty(max(ws_bytes // 4, 1), dtype=torch.float32, device=dev)
+
+
+def _stft_mag(xs, fft_size, hop_size, win, win_length, eps):
+    n, T = xs.shape
+    out = torch.empty(n, num_frames(T, hop_size), fft_size // 2 + 1, dtype=torch.float32, device=xs.device)
+    native.check(native.lib().adk_stft_mag(_ptr(xs), n, T, fft_size, hop_size, _ptr(win), win_length, float(eps), _ptr(out),
+                                           native.current_stream(xs.device)), "adk_stft_mag")
+    return out
+
+
+class _StftMagFn(torch.autograd.Function):
+    """stft() with a backward: adk_stft_mag, and adk_grad_stft_mag on the saved signal."""
+
+    @staticmethod
+    def forward(ctx, x, xs, win, args):
+        ctx.args, ctx.like = args, (x.shape, x.device, x.dtype)
+        ctx.save_for_backward(xs, win)
+        return _stft_mag(xs, args[0], args[1], win, args[2], args[3])
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        (xs, win), (fft_size, hop_size, win_length, eps), (shape, device, dtype) = ctx.saved_tensors, ctx.args, ctx.like
+        dev = xs.device
+        n, T = int(xs.shape[0]), int(xs.shape[1])
+        g = g.to(device=dev, dtype=torch.float32).contiguous()
+        grad = torch.empty_like(xs)
+        ws = _grad_workspace(n, T, fft_size, hop_size, dev)
+        native.check(native.lib().adk_grad_stft_mag(_ptr(xs), _ptr(g), n, T, fft_size, hop_size, _ptr(win), win_length, float(eps),
+                                                   _ptr(ws), _ptr(grad), native.current_stream(dev)), "adk_grad_stft_mag")
+        return grad.reshape(shape).to(device=device, dtype=dtype), None, None, None
+
+
+class _StftLossFn(torch.autograd.Function):
+    """(sc, mag) of a list of STFTLoss resolutions with a backward with respect to x: the fold path's values, the forward's (R, 3)
+    f64 sums kept on the device, and per resolution adk_grad_stft_distance with scale_sc = 1 / R and scale_mag = 1 / (R count),
+    summed over the resolutions in their order."""
+
+    @staticmethod
+    def forward(ctx, x, losses, a, b):
+        ctx.losses, ctx.like = losses, (x.shape, x.device, x.dtype)
+        sc, mag, sums = _loss_value(losses, a, b)
+        ctx.save_for_backward(a, b, sums)
+        return sc, mag
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_sc, g_mag):
+        (a, b, sums), losses, (shape, device, dtype) = ctx.saved_tensors, ctx.losses, ctx.like
+        up = torch.stack([g_sc.reshape(()), g_mag.reshape(())]).to(device=a.device, dtype=torch.float32).contiguous()
+        R = len(losses)
+        grad = None
+        for r, f in enumerate(losses):
+            count = a.shape[0] * f.num_frames(a.shape[1]) * (f.fft_size // 2 + 1)
+            gr = f._distance_grad(a, b, sums[r], 1.0 / R, up[0:1], 1.0 / (float(count) * R), up[1:2])
+            grad = gr if grad is None else grad + gr
+        return grad.reshape(shape).to(device=device, dtype=dtype), None, None, None
+
+
+def _loss_value(losses, a, b):
+    """(sc, mag, sums): the means over the resolutions `losses` of the two terms as 0-d float32 device tensors, and the (R, 3)
+    float64 sums the folds left on the device."""
+    dev = a.device
+    R = len(losses)
+    sums = torch.zeros(R, 3, dtype=torch.float64, device=dev)
+    counts = torch.zeros(R, dtype=torch.int64, device=dev)
+    res = torch.empty(R, 2, dtype=torch.float32, device=dev)
+    for r, f in enumerate(losses):
+        f.fold(a, b, sums[r], counts[r:r + 1], res[r, 0:1], res[r, 1:2])
+    return _mean_f32(res[:, 0]), _mean_f32(res[:, 1]), sums
+
+
+def _prepare(losses, x, y, differentiable):
+    """Settled, validated, contiguous float32 (n, T) signals on the device of the resolutions `losses`."""
+    _no_grad_inputs(y) if _wants_grad(differentiable, x) else _no_grad_inputs(x, y)
+    x, y = _settled(x), _settled(y)
+    if tuple(x.shape) != tuple(y.shape):
+        raise ValueError(f"x {tuple(x.shape)} and y {tuple(y.shape)} must have the same shape")
+    for f in losses:
+        f.check_length(y.shape[-1])
+    dev = losses[0]._device_for(y)
+    for f in losses:
+        f.to(dev)
+    return _signals(x.detach(), dev), _signals(y, dev)
+
+
+def _forward(losses, x, y, differentiable):
+    a, b = _prepare(losses, x, y, differentiable)
+    if _wants_grad(differentiable, x):
+        if a.shape[0] == 0:
+            raise ValueError("an empty batch has no gradient")
+        return _StftLossFn.apply(lazy_guard.plain(x), losses, a, b)
+    return _loss_value(losses, a, b)[:2]
+
+
+def stft(x, fft_size, hop_size, win_length, window, eps=1e-7, differentiable=False):
     """losses/stft_loss.py:19-35: x (B, T), window a (win_length,) tensor -> magnitudes (B, frames, fft_size // 2 + 1) float32
-    on the device.  Does not synchronise."""
+    on the device.  Does not synchronise.  ``differentiable=True`` (not in the reference, whose function always is): an ``x`` that
+    requires grad gets one (adk_grad_stft_mag)."""
     fft_size, hop_size, win_length = int(fft_size), int(hop_size), int(win_length)
     _check_fft_size(fft_size)
-    _no_grad_inputs(x)
+    grad = _wants_grad(differentiable, x)
+    if not grad:
+        _no_grad_inputs(x)
     x = _settled(x)
     if x.dim() != 2:
         raise ValueError(f"expected a (B, T) waveform, got shape {tuple(x.shape)}")
@@ -34,13 +143,13 @@ def stft(x, fft_size, hop_size, win_length, window, eps=1e-7):
                          f"{win_length}, {tuple(window.shape)}")
     _check_length(x.shape[-1], fft_size)
     dev = _device_of(x)
-    xs = _signals(x, dev)
-    win = window.to(device=dev, dtype=torch.float32).contiguous()
-    n, T = xs.shape
-    out = torch.empty(n, num_frames(T, hop_size), fft_size // 2 + 1, dtype=torch.float32, device=dev)
-    native.check(native.lib().adk_stft_mag(_ptr(xs), n, T, fft_size, hop_size, _ptr(win), win_length, float(eps), _ptr(out),
-                                           native.current_stream(dev)), "adk_stft_mag")
-    return out
+    xs = _signals(x.detach(), dev)
+    win = window.detach().to(device=dev, dtype=torch.float32).contiguous()
+    if grad:
+        if xs.shape[0] == 0:
+            raise ValueError("an empty batch has no gradient")
+        return _StftMagFn.apply(x, xs, win, (fft_size, hop_size, win_length, float(eps)))
+    return _stft_mag(xs, fft_size, hop_size, win, win_length, eps)
 
 
 def _mag_distance(x_mag, y_mag):
@@ -82,9 +191,12 @@ class LogSTFTMagnitudeLoss:
 
 
 class STFTLoss:
-    """losses/stft_loss.py:80-117 on the HIP path.  Same arguments and defaults; ``forward(x, y)`` returns ``(sc, mag)``."""
+    """losses/stft_loss.py:80-117 on the HIP path.  Same arguments and defaults; ``forward(x, y)`` returns ``(sc, mag)``.
+    ``differentiable=True`` (not in the reference, whose modules always are): an ``x`` that requires grad gets a gradient from
+    both terms (adk_grad_stft_distance); ``y`` is the target and may not require grad.  The values are the same either way."""
 
-    def __init__(self, fft_size=1024, hop_size=120, win_length=600, window="hann_window", device=None):
+    def __init__(self, fft_size=1024, hop_size=120, win_length=600, window="hann_window", device=None, differentiable=False):
+        self.differentiable = bool(differentiable)
         self.fft_size, self.hop_size, self.win_length = int(fft_size), int(hop_size), int(win_length)
         _check_fft_size(self.fft_size)
         if self.hop_size <= 0 or not 0 < self.win_length <= self.fft_size:
@@ -126,31 +238,37 @@ class STFTLoss:
                                            self.win_length, float(self.eps), _ptr(sums), _ptr(count), _ptr(ws), _ptr(sc), _ptr(mag),
                                            native.current_stream(dev)), "adk_stft_distance")
 
+    def _distance_grad(self, x, y, sums, scale_sc, up_sc, scale_mag, up_mag):
+        """adk_grad_stft_distance: the gradient with respect to x of scale_sc up_sc[0] sc + scale_mag up_mag[0] sum |dlog|, sums
+        (float64 [3]) being what fold(x, y, ...) left on the device; up_sc, up_mag float32 [1] on the device."""
+        dev = self._dev
+        n, T = int(x.shape[0]), int(x.shape[1])
+        grad = torch.empty_like(x)
+        ws = _grad_workspace(n, T, self.fft_size, self.hop_size, dev)
+        native.check(native.lib().adk_grad_stft_distance(_ptr(x), _ptr(y), n, T, self.fft_size, self.hop_size, _ptr(self._window_d),
+                                                         self.win_length, float(self.eps), _ptr(sums), float(scale_sc), _ptr(up_sc),
+                                                         float(scale_mag), _ptr(up_mag), _ptr(ws), _ptr(grad),
+                                                         native.current_stream(dev)), "adk_grad_stft_distance")
+        return grad
+
     def forward(self, x, y):
-        _no_grad_inputs(x, y)
-        x, y = _settled(x), _settled(y)
-        if tuple(x.shape) != tuple(y.shape):
-            raise ValueError(f"x {tuple(x.shape)} and y {tuple(y.shape)} must have the same shape")
-        self.check_length(y.shape[-1])
-        dev = self._device_for(y)
-        a, b = _signals(x, dev), _signals(y, dev)
-        sums = torch.zeros(3, dtype=torch.float64, device=dev)
-        count = torch.zeros(1, dtype=torch.int64, device=dev)
-        res = torch.empty(2, dtype=torch.float32, device=dev)
-        self.fold(a, b, sums, count, res[0:1], res[1:2])
-        return res[0], res[1]
+        return _forward([self], x, y, self.differentiable)
 
     __call__ = forward
 
 
 class MultiResolutionSTFTLoss:
     """losses/stft_loss.py:120-170 on the HIP path: the means over resolutions of the two terms.  Same arguments and defaults;
-    ``forward(x, y)`` returns ``(sc_loss, mag_loss)`` as 0-d float32 tensors on the device without synchronising."""
+    ``forward(x, y)`` returns ``(sc_loss, mag_loss)`` as 0-d float32 tensors on the device without synchronising.
+    ``differentiable=True`` (not in the reference): an ``x`` that requires grad gets a gradient from both terms, the
+    resolutions' gradients added in their order; ``y`` may not require grad.  The values are the same either way."""
 
     def __init__(self, fft_sizes=[1024, 2048, 512], hop_sizes=[120, 240, 50], win_lengths=[600, 1200, 240], window="hann_window",
-                 device=None):
+                 device=None, differentiable=False):
         assert len(fft_sizes) == len(hop_sizes) == len(win_lengths)
-        self.stft_losses = [STFTLoss(f, h, w, window, device=device) for f, h, w in zip(fft_sizes, hop_sizes, win_lengths)]
+        self.differentiable = bool(differentiable)
+        self.stft_losses = [STFTLoss(f, h, w, window, device=device, differentiable=differentiable)
+                            for f, h, w in zip(fft_sizes, hop_sizes, win_lengths)]
 
     def to(self, device):
         for f in self.stft_losses:
@@ -163,26 +281,10 @@ class MultiResolutionSTFTLoss:
 
     def prepare(self, x, y):
         """Settled, validated, contiguous float32 (n, T) signals on the loss's device."""
-        _no_grad_inputs(x, y)
-        x, y = _settled(x), _settled(y)
-        if tuple(x.shape) != tuple(y.shape):
-            raise ValueError(f"x {tuple(x.shape)} and y {tuple(y.shape)} must have the same shape")
-        for f in self.stft_losses:
-            f.check_length(y.shape[-1])
-        dev = self.stft_losses[0]._device_for(y)
-        self.to(dev)
-        return _signals(x, dev), _signals(y, dev)
+        return _prepare(self.stft_losses, x, y, self.differentiable)
 
     def forward(self, x, y):
-        a, b = self.prepare(x, y)
-        dev = self.device
-        R = len(self.stft_losses)
-        sums = torch.zeros(R, 3, dtype=torch.float64, device=dev)
-        counts = torch.zeros(R, dtype=torch.int64, device=dev)
-        res = torch.empty(R, 2, dtype=torch.float32, device=dev)
-        for r, f in enumerate(self.stft_losses):
-            f.fold(a, b, sums[r], counts[r:r + 1], res[r, 0:1], res[r, 1:2])
-        return _mean_f32(res[:, 0]), _mean_f32(res[:, 1])
+        return _forward(self.stft_losses, x, y, self.differentiable)
 
     __call__ = forward
 
@@ -226,9 +328,9 @@ class STFTDistance:
             return float(np.mean(np.sqrt(s[:, 0]) / np.sqrt(s[:, 1]))), float(np.mean(s[:, 2] / c))
 
 
-def from_config(config, device=None):
+def from_config(config, device=None, differentiable=False):
     """The loss a training config enables: MultiResolutionSTFTLoss(**config['stft_loss_params']) when ``use_stft_loss`` is
     true, else None."""
     if not config.get("use_stft_loss", False):
         return None
-    return MultiResolutionSTFTLoss(**config["stft_loss_params"], device=device)
+    return MultiResolutionSTFTLoss(**config["stft_loss_params"], device=device, differentiable=differentiable)

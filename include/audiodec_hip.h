@@ -397,6 +397,37 @@ int adk_shape_distance(const float* y_hat, const float* y, int32_t n_signals, in
                        int64_t* count, void* workspace, float* loss, void* stream);
 
 /*
+ * STFT loss and waveform-shape loss, backward (the adk_grad_* entry points, each named after the forward entry point it
+ * differentiates): the vector-Jacobian products of the operations above with respect to the predicted
+ * signal (x, y_hat) only, as torch's autograd defines them for losses/stft_loss.py and losses/waveform_loss.py (clamp passes the
+ * gradient where its input >= eps; MaxPool1d passes it to the first maximum of a window).  Shared arguments mean the same.
+ * adk_grad_stft_mag: g [n_signals][frames][n_fft/2 + 1] f32 is the gradient of adk_stft_mag's out; grad_x [n_signals][n_samples]
+ * f32 = sum over out of g d out / d x.  adk_grad_stft_distance: grad_x = the gradient with respect to x of
+ *   scale_sc up_sc[0] sqrt(S0) / sqrt(S1)  +  scale_mag up_mag[0] S2
+ * with (S0, S1, S2) the three sums of adk_stft_distance over (x, y).  Per magnitude bin that is the product above with
+ *   g = c_sc (x_mag - y_mag) - c_mag sgn / x_mag,   c_sc = (float)(scale_sc up_sc[0] / sqrt(S0 S1)), 0 where S0 == 0,
+ *   c_mag = (float)(scale_mag up_mag[0]),   sgn = sign of the forward's own f32 term log y_mag - log x_mag (sign(0) = 0),
+ * S0 = sums[0] and S1 = sums[1] being read on the device from the accumulator adk_stft_distance folded (x, y) into (3 doubles,
+ * 8-byte aligned), up_sc / up_mag device pointers to one f32 each: nothing is read back to the host.  For the mean over R
+ * resolutions, scale_sc = 1 / R and scale_mag = 1 / (R count).  Each frame's forward is recomputed (no spectra are kept); its
+ * windowed gradient goes to workspace [n_signals][frames][n_fft] f32 = adk_grad_stft_workspace_bytes(...) bytes, 4-byte aligned,
+ * any contents; a second launch gathers every sample's contributions through the reflect padding in ascending frame order.
+ * adk_grad_shape_distance: grad [n_signals][n_samples] = the gradient with respect to y_hat of c sum |a - b|, c = (float)(scale *
+ * upstream[0]): sign(a - b) sign(y_hat[i]) c at the first index i of each window's max |y_hat|, 0 at every other sample and in the
+ * dropped tail.  For the mean over R window lengths, scale = 1 / (R n_signals windows).
+ * No float atomics: bitwise reproducible.  grad is fully written.  n_signals == 0 is a no-op.  Same limits as the forward; every
+ * argument is checked before any HIP call (ADK_ERR_ARG).  No allocation, no synchronisation.
+ */
+int64_t adk_grad_stft_workspace_bytes(int32_t n_signals, int32_t n_samples, int32_t n_fft, int32_t hop);
+int adk_grad_stft_mag(const float* x, const float* g, int32_t n_signals, int32_t n_samples, int32_t n_fft, int32_t hop,
+                     const float* window, int32_t win_length, float eps, void* workspace, float* grad_x, void* stream);
+int adk_grad_stft_distance(const float* x, const float* y, int32_t n_signals, int32_t n_samples, int32_t n_fft, int32_t hop,
+                           const float* window, int32_t win_length, float eps, const double* sums, double scale_sc,
+                           const float* up_sc, double scale_mag, const float* up_mag, void* workspace, float* grad_x, void* stream);
+int adk_grad_shape_distance(const float* y_hat, const float* y, int32_t n_signals, int32_t n_samples, int32_t winlen, double scale,
+                            const float* upstream, float* grad, void* stream);
+
+/*
  * Bit-packed code wire format (the reference passes the int64 index tensor through a
  * queue.Queue, bin/stream.py:224,230, and never serialises it).  One frame of one stream = n_q codes of
  * `bits` bits, LSB-first: code q (= emitted index - size*q) occupies bits [q*bits, (q+1)*bits) of the
