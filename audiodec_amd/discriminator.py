@@ -15,7 +15,14 @@ State dicts use the reference's keys.  The scale discriminator's layers are ``nn
 keys whatever ``follow_official_norm`` says.  The period discriminator's layers carry weight norm (``weight_g``/``weight_v``),
 folded once at load as ``torch._weight_norm(v, g, 0)``.
 
-Forward only: an input that requires grad while grad is enabled raises NotImplementedError.
+Forward only by default: an input that requires grad while grad is enabled raises NotImplementedError.  With
+``differentiable=True`` (not in the reference, whose modules always are) the discriminators, ``GeneratorAdversarialLoss``,
+``FeatureMatchLoss`` and ``AdversarialEval`` give the generated waveform ``y_hat`` a gradient through ``torch.autograd``: each conv
+(with its activation) and each padding / pooling step is a Function whose backward is adk_disc_conv_grad / adk_disc_prep_grad,
+and each loss reduction one whose backward is adk_disc_loss_grad.  The discriminator's weights stay constants (no dW), the natural
+side ``y`` may never require grad, and the backward is once-differentiable and bitwise reproducible.  A differentiable pass keeps
+the ``y_hat`` feature pyramid alive until backward (the leaky masks are taken from the saved layer outputs).
+``DiscriminatorAdversarialLoss`` and ``AdversarialEval.update`` stay forward only.
 """
 import copy
 import ctypes as C
@@ -179,16 +186,60 @@ def _no_grad_inputs(*ts):
         raise NotImplementedError("the HIP discriminator is forward only: run it under torch.no_grad() or detach the inputs")
 
 
+def _wants_grad(differentiable, *ts):
+    return bool(differentiable) and torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in ts)
+
+
+def pack_grad_weights(w, layer):
+    """The backward-data GEMM's weights of one layer from its (C_out, C_in/g, k) weight: [g][phase r < stride][kk][m], where
+    phase r holds the taps t = r, r + stride, ... (the only ones that reach an input row h with (h + pad) % stride == r),
+    kk = co * taps(r) + tt and m = ci.  Flat (g, C_out/g * k, C_in/g): the phases of a group follow each other."""
+    g, s = layer.groups, layer.stride
+    cout_g, cin_g, k = layer.cout // g, layer.cin // g, layer.kernel
+    w = w.reshape(g, cout_g, cin_g, k)
+    phases = [w[:, :, :, r::s].permute(0, 1, 3, 2).reshape(g, -1, cin_g) for r in range(min(s, k))]
+    return torch.cat(phases, 1).contiguous()
+
+
+def _check_slopes(layers, differentiable):
+    if differentiable and any(L.act_slope is not None and L.act_slope < 0 for L in layers):
+        raise ValueError("differentiable=True needs negative_slope >= 0: the backward takes the LeakyReLU mask from the layer's output")
+
+
 class _Conv:
     """One layer's device weights."""
 
     def __init__(self, layer, w, b, dev):
         self.layer, self.impl = layer, conv_impl(layer)
+        self._w_grad = None                                                    # the backward's GEMM packing, made on first use
         if self.impl == IMPL_GEMM:
             g = layer.groups
             w = w.reshape(g, layer.cout // g, -1).permute(0, 2, 1)             # [g][cin_g * k][cout_g]
         self.w = w.contiguous().to(dev)
         self.b = b.float().contiguous().to(dev) if b is not None else None
+
+    def grad_weights(self):
+        """The weights adk_disc_conv_grad reads: the reference's layout for the direct kernel, pack_grad_weights for the GEMM
+        (re-packed once, on the device, from the forward packing)."""
+        if self.impl != IMPL_GEMM:
+            return self.w
+        if self._w_grad is None:
+            L = self.layer
+            w = self.w.permute(0, 2, 1).reshape(L.cout, L.cin // L.groups, L.kernel)
+            self._w_grad = pack_grad_weights(w, L)
+        return self._w_grad
+
+    def grad(self, dy, y, x_shape):
+        """dy, y (N, C_out, H', P) contiguous float32 -> dx of x_shape (N, C_in, H, P)."""
+        L = self.layer
+        n, cin, h, p = x_shape
+        dx = torch.empty(n, cin, h, p, dtype=torch.float32, device=dy.device)
+        act = ACT_LEAKY if L.act_slope is not None else ACT_NONE
+        native.check(native.lib().adk_disc_conv_grad(_ptr(dy), _ptr(y) if act else None, _ptr(self.grad_weights()), _ptr(dx), n, cin,
+                                                      h, p, L.cout, L.groups, L.kernel, L.stride, L.pad, act,
+                                                      float(L.act_slope or 0.0), self.impl, native.current_stream(dy.device)),
+                     "adk_disc_conv_grad")
+        return dx
 
     def __call__(self, x):
         """x (N, C_in, H, P) contiguous float32 -> (N, C_out, H', P)."""
@@ -209,6 +260,54 @@ def _prep(x, rows, n_in, op, a, b=0, c=0, n_out=None):
     y = torch.empty(rows, n_out, dtype=torch.float32, device=x.device)
     native.check(native.lib().adk_disc_prep(_ptr(x), _ptr(y), rows, n_in, op, a, b, c, native.current_stream(x.device)), "adk_disc_prep")
     return y
+
+
+class _ConvFn(torch.autograd.Function):
+    """One conv layer (with its activation) with a backward to its input: adk_disc_conv, and adk_disc_conv_grad on the saved output."""
+
+    @staticmethod
+    def forward(ctx, x, conv):
+        ctx.conv, ctx.x_shape = conv, tuple(x.shape)
+        y = conv(x)
+        if conv.layer.act_slope is not None:
+            ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        y = ctx.saved_tensors[0] if ctx.saved_tensors else None
+        return ctx.conv.grad(dy.to(torch.float32).contiguous(), y, ctx.x_shape), None
+
+
+class _PrepFn(torch.autograd.Function):
+    """One adk_disc_prep op on (rows, n_in) with a backward: adk_disc_prep_grad."""
+
+    @staticmethod
+    def forward(ctx, x, args):
+        ctx.args = args
+        rows, n_in, op, a, b, c, n_out = args
+        return _prep(x, rows, n_in, op, a, b, c, n_out=n_out)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        rows, n_in, op, a, b, c, n_out = ctx.args
+        dy = dy.to(torch.float32).contiguous()
+        dx = torch.empty(rows, n_in, dtype=torch.float32, device=dy.device)
+        native.check(native.lib().adk_disc_prep_grad(_ptr(dy), _ptr(dx), rows, n_in, op, a, b, c, native.current_stream(dy.device)),
+                     "adk_disc_prep_grad")
+        return dx, None
+
+
+def _conv_op(conv, h, grad):
+    return _ConvFn.apply(h, conv) if grad else conv(h)
+
+
+def _prep_op(x, rows, n_in, op, a, b=0, c=0, n_out=None, grad=False):
+    if grad:
+        return _PrepFn.apply(x.reshape(rows, n_in), (rows, n_in, op, a, b, c, n_out))
+    return _prep(x, rows, n_in, op, a, b, c, n_out=n_out)
 
 
 class _Module:
@@ -290,7 +389,8 @@ class _Module:
         return self._dev
 
     def _prepare(self, x):
-        _no_grad_inputs(x)
+        if not _wants_grad(getattr(self, "differentiable", False), x):
+            _no_grad_inputs(x)
         x = _settled(x)
         if self._host is None:
             raise RuntimeError(f"{type(self).__name__}: no weights loaded (call load_state_dict first)")
@@ -318,7 +418,8 @@ class HiFiGANMultiScaleDiscriminator(_Module):
     """discriminator.py:346-449 on the HIP path.  Same arguments and defaults; only AvgPool1d pooling is implemented."""
 
     def __init__(self, scales=3, downsample_pooling="AvgPool1d", downsample_pooling_params=POOL_DEFAULTS,
-                 discriminator_params=MSD_DISC_DEFAULTS, follow_official_norm=False, device=None, _prefix=""):
+                 discriminator_params=MSD_DISC_DEFAULTS, follow_official_norm=False, device=None, differentiable=False, _prefix=""):
+        self.differentiable = bool(differentiable)
         if downsample_pooling != "AvgPool1d":
             raise NotImplementedError(f"downsample_pooling {downsample_pooling!r}: the HIP path implements AvgPool1d only")
         pp = dict(downsample_pooling_params)
@@ -333,52 +434,58 @@ class HiFiGANMultiScaleDiscriminator(_Module):
             if follow_official_norm:                  # no effect on parameters: the layers are Conv1d (module docstring)
                 params["use_weight_norm"], params["use_spectral_norm"] = (False, True) if i == 0 else (True, False)
             self.discriminator_layers.append(scale_layers(f"{_prefix}discriminators.{i}.", **params))
+        _check_slopes([L for ls in self.discriminator_layers for L in ls], self.differentiable)
         self._init_layers([L for ls in self.discriminator_layers for L in ls], device)
 
     def layers_of(self, x, d0=0, prepared=False):
         """Yields (sub-discriminator index + d0, layer, tensor, layers of that sub-discriminator) in the reference's order, one
         layer at a time (a caller that drops each tensor never holds the whole feature pyramid)."""
         x = x if prepared else self._prepare(x)
+        grad = _wants_grad(self.differentiable, x)
         b, c, t = x.shape
         cur, n = x, t
         for d, layers in enumerate(self.discriminator_layers):
             h = cur.reshape(b, c, n, 1)
             for l, L in enumerate(layers):
-                h = self._convs[L.key](h)
+                h = _conv_op(self._convs[L.key], h, grad)
                 yield d0 + d, l, h.reshape(h.shape[0], h.shape[1], h.shape[2]), len(layers)
             if d + 1 < len(self.discriminator_layers):
                 k, s, p = self.pool
                 n2 = pool_out_len(n, k, s, p)
                 if n2 < 1:
                     raise ValueError(f"input length {t}: too short for {self.scales} scales")
-                cur = _prep(cur, b * c, n, PREP_AVGPOOL, k, s, p, n_out=n2).reshape(b, c, n2)
+                cur = _prep_op(cur, b * c, n, PREP_AVGPOOL, k, s, p, n_out=n2, grad=grad).reshape(b, c, n2)
                 n = n2
 
 
 class HiFiGANMultiPeriodDiscriminator(_Module):
     """discriminator.py:160-210 on the HIP path.  Same arguments and defaults."""
 
-    def __init__(self, periods=[2, 3, 5, 7, 11], discriminator_params=MPD_DISC_DEFAULTS, device=None, _prefix=""):
+    def __init__(self, periods=[2, 3, 5, 7, 11], discriminator_params=MPD_DISC_DEFAULTS, device=None, differentiable=False,
+                 _prefix=""):
+        self.differentiable = bool(differentiable)
         self.periods = [int(p) for p in periods]
         self.discriminator_layers = []
         for i, period in enumerate(self.periods):
             params = copy.deepcopy(dict(discriminator_params))
             params["period"] = period
             self.discriminator_layers.append(period_layers(f"{_prefix}discriminators.{i}.", **params))
+        _check_slopes([L for ls in self.discriminator_layers for L in ls], self.differentiable)
         self._init_layers([L for ls in self.discriminator_layers for L in ls], device)
 
     def layers_of(self, x, d0=0, prepared=False):
         x = x if prepared else self._prepare(x)
+        grad = _wants_grad(self.differentiable, x)
         b, c, t = x.shape
         for d, (p, layers) in enumerate(zip(self.periods, self.discriminator_layers)):
             n_pad = reflect_pad_len(t, p)
             if n_pad >= t:
                 raise ValueError(f"input length {t}: reflect padding of {n_pad} for period {p} needs more than {n_pad} samples "
                                  "(F.pad raises for it too)")
-            xp = _prep(x, b * c, t, PREP_REFLECT, n_pad, n_out=t + n_pad) if n_pad else x
+            xp = _prep_op(x, b * c, t, PREP_REFLECT, n_pad, n_out=t + n_pad, grad=grad) if n_pad else x
             h = xp.reshape(b, c, (t + n_pad) // p, p)
             for l, L in enumerate(layers):
-                h = self._convs[L.key](h)
+                h = _conv_op(self._convs[L.key], h, grad)
                 out = h if l + 1 < len(layers) else h.reshape(b, -1)          # torch.flatten(x, 1, -1)
                 yield d0 + d, l, out, len(layers)
 
@@ -389,12 +496,15 @@ class Discriminator(_Module):
 
     def __init__(self, scales=3, scale_downsample_pooling="AvgPool1d", scale_downsample_pooling_params=POOL_DEFAULTS,
                  scale_discriminator_params=MSD_DISC_DEFAULTS, follow_official_norm=True, periods=[2, 3, 5, 7, 11],
-                 period_discriminator_params=MPD_DISC_DEFAULTS, device=None):
+                 period_discriminator_params=MPD_DISC_DEFAULTS, device=None, differentiable=False):
+        self.differentiable = bool(differentiable)
         self.msd = HiFiGANMultiScaleDiscriminator(scales=scales, downsample_pooling=scale_downsample_pooling,
                                                   downsample_pooling_params=scale_downsample_pooling_params,
                                                   discriminator_params=scale_discriminator_params,
-                                                  follow_official_norm=follow_official_norm, _prefix="msd.")
-        self.mpd = HiFiGANMultiPeriodDiscriminator(periods=periods, discriminator_params=period_discriminator_params, _prefix="mpd.")
+                                                  follow_official_norm=follow_official_norm, differentiable=differentiable,
+                                                  _prefix="msd.")
+        self.mpd = HiFiGANMultiPeriodDiscriminator(periods=periods, discriminator_params=period_discriminator_params,
+                                                   differentiable=differentiable, _prefix="mpd.")
         self.discriminator_layers = self.msd.discriminator_layers + self.mpd.discriminator_layers
         self._init_layers(self.msd._layers + self.mpd._layers, device, children=[self.msd, self.mpd])
 
@@ -442,13 +552,48 @@ class _Terms:
         return self.sum / self.count.to(torch.float64)
 
 
+class _LossFn(torch.autograd.Function):
+    """Loss values with a backward to the generated side's tensors.  ``value()`` returns the tuple of 0-d float32 values (the
+    forward-only code's); ``terms`` is a list of (input index, a, b, kind, coef, weights): the term contributes
+    coef * sum_i term(a[i], b[i]) to the outputs k of weights = {k: factor}, scaled by factor.  backward: per term
+    adk_disc_loss_grad with the upstream sum_k factor_k g_k, formed and read on the device; terms of one input are added in order."""
+
+    @staticmethod
+    def forward(ctx, value, terms, *hats):
+        ctx.terms, ctx.like = terms, [(h.shape, h.device, h.dtype) for h in hats]
+        return value()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *gs):
+        grads = [None] * len(ctx.like)
+        lib = native.lib()
+        for i, a, b, kind, coef, weights in ctx.terms:
+            if not ctx.needs_input_grad[2 + i]:
+                continue
+            up = None
+            for k, f in weights.items():
+                g = gs[k].reshape(1).to(device=a.device, dtype=torch.float32)
+                g = g if f == 1.0 else g * f
+                up = g if up is None else up + g
+            out = torch.empty_like(a)
+            native.check(lib.adk_disc_loss_grad(_ptr(a), _ptr(b), a.numel(), kind, float(coef), _ptr(up.contiguous()), _ptr(out),
+                                                native.current_stream(a.device)), "adk_disc_loss_grad")
+            grads[i] = out if grads[i] is None else grads[i] + out
+        res = []
+        for g, (shape, device, dtype) in zip(grads, ctx.like):
+            res.append(None if g is None else g.reshape(shape).to(device=device, dtype=dtype))
+        return (None, None, *res)
+
+
 def _final(o):
     return o[-1] if isinstance(o, (tuple, list)) else o
 
 
-def _flat(t):
+def _flat(t, grad_ok=False):
     t = _settled(t)
-    _no_grad_inputs(t)
+    if not grad_ok:
+        _no_grad_inputs(t)
     return t.detach().to(torch.float32).contiguous()
 
 
@@ -464,26 +609,41 @@ class GeneratorAdversarialLoss:
     """losses/adversarial_loss.py GeneratorAdversarialLoss on the HIP path: sum (or mean) over discriminators of
     mse(D(y_hat), 1) or -mean(D(y_hat)); each discriminator's final output is reduced by adk_disc_loss."""
 
-    def __init__(self, average_by_discriminators=True, loss_type="mse"):
+    def __init__(self, average_by_discriminators=True, loss_type="mse", differentiable=False):
         _check_loss_type(loss_type)
         self.average_by_discriminators = average_by_discriminators
         self.loss_type = loss_type
+        self.differentiable = bool(differentiable)
 
     def kind(self):
         return (LOSS_MSE_ONE, 1.0) if self.loss_type == "mse" else (LOSS_SUM, -1.0)
 
+    def coef(self, count, n_discriminators):
+        """d loss / d (sum of the term over one discriminator's final output of `count` elements)."""
+        return self.kind()[1] / count / (n_discriminators if self.average_by_discriminators else 1)
+
     def forward(self, outputs):
         outs = _as_list(outputs)
         outs = [_final(o) for o in outs] if outs is not None else [outputs]
-        ts = [_flat(o) for o in outs]
-        terms = _Terms(len(ts), ts[0].device)
-        kind, sign = self.kind()
-        for i, t in enumerate(ts):
-            terms.fold(i, t, kind)
-        v = terms.means().sum() * sign
-        if _as_list(outputs) is not None and self.average_by_discriminators:
-            v = v / len(ts)
-        return v.to(torch.float32)
+        grad = _wants_grad(self.differentiable, *outs)
+        ts = [_flat(o, grad) for o in outs]
+        averaged = _as_list(outputs) is not None and self.average_by_discriminators
+
+        def value():
+            terms = _Terms(len(ts), ts[0].device)
+            kind, sign = self.kind()
+            for i, t in enumerate(ts):
+                terms.fold(i, t, kind)
+            v = terms.means().sum() * sign
+            if averaged:
+                v = v / len(ts)
+            return v.to(torch.float32)
+
+        if not grad:
+            return value()
+        terms = [(i, t, None, self.kind()[0], self.kind()[1] / t.numel() / (len(ts) if averaged else 1), {0: 1.0})
+                 for i, t in enumerate(ts) if t.numel()]
+        return _LossFn.apply(lambda: (value(),), terms, *[lazy_guard.plain(o) for o in outs])[0]
 
     __call__ = forward
 
@@ -525,10 +685,11 @@ class FeatureMatchLoss:
     """losses/feat_match_loss.py FeatureMatchLoss on the HIP path: per discriminator the sum (or mean) over layers of
     F.l1_loss(feat_hat, feat), summed (or averaged) over discriminators."""
 
-    def __init__(self, average_by_layers=True, average_by_discriminators=True, include_final_outputs=False):
+    def __init__(self, average_by_layers=True, average_by_discriminators=True, include_final_outputs=False, differentiable=False):
         self.average_by_layers = average_by_layers
         self.average_by_discriminators = average_by_discriminators
         self.include_final_outputs = include_final_outputs
+        self.differentiable = bool(differentiable)
 
     def layers_used(self, n_layers):
         return n_layers if self.include_final_outputs else n_layers - 1
@@ -546,24 +707,43 @@ class FeatureMatchLoss:
             total = total / len(layout)
         return total
 
+    def coefs(self, counts, layout):
+        """d loss / d (sum of |a - b| over one used feature map), in the order of the terms: counts = elements per term."""
+        out, i = [], 0
+        for n in layout:
+            for c in counts[i:i + n]:
+                out.append(1.0 / c / (n if self.average_by_layers else 1) / (len(layout) if self.average_by_discriminators else 1))
+            i += n
+        return out
+
     def forward(self, feats_hat, feats):
-        pairs, layout = [], []
+        raw, layout = [], []
         for fh, f in zip(feats_hat, feats):
             fh, f = list(fh), list(f)
             if not self.include_final_outputs:
                 fh, f = fh[:-1], f[:-1]
             used = list(zip(fh, f))
             layout.append(len(used))
-            for a, b in used:
-                a, b = _flat(a), _flat(b)
-                if a.shape != b.shape:
-                    raise ValueError(f"feature shapes differ: {tuple(a.shape)} vs {tuple(b.shape)}")
-                pairs.append((a, b))
-        dev = pairs[0][0].device
-        terms = _Terms(len(pairs), dev)
-        for i, (a, b) in enumerate(pairs):
-            terms.fold(i, a, LOSS_L1, b)
-        return self.combine(terms.means(), layout).to(torch.float32)
+            raw += used
+        grad = _wants_grad(self.differentiable, *[a for a, _ in raw])
+        pairs = []
+        for a, b in raw:
+            a, b = _flat(a, grad), _flat(b)
+            if a.shape != b.shape:
+                raise ValueError(f"feature shapes differ: {tuple(a.shape)} vs {tuple(b.shape)}")
+            pairs.append((a, b))
+
+        def value():
+            terms = _Terms(len(pairs), pairs[0][0].device)
+            for i, (a, b) in enumerate(pairs):
+                terms.fold(i, a, LOSS_L1, b)
+            return self.combine(terms.means(), layout).to(torch.float32)
+
+        if not grad:
+            return value()
+        coefs = self.coefs([a.numel() for a, _ in pairs], layout)
+        terms = [(i, a, b, LOSS_L1, coefs[i], {0: 1.0}) for i, (a, b) in enumerate(pairs) if a.numel()]
+        return _LossFn.apply(lambda: (value(),), terms, *[lazy_guard.plain(a) for a, _ in raw])[0]
 
     __call__ = forward
 
@@ -579,11 +759,19 @@ class AdversarialEval:
     Each layer's feature-matching term is folded as soon as the layer is produced and the layer is dropped, so the feature
     pyramid is never held whole.  ``forward(y_hat, y)`` returns 0-d float32 device tensors for one batch without synchronising;
     ``update(y_hat, y)`` folds a batch into device-side totals and ``value()`` returns the values of all folded batches as one
-    batch (floats; synchronises), like mel.MelDistance; ``reset()`` zeroes the totals."""
+    batch (floats; synchronises), like mel.MelDistance; ``reset()`` zeroes the totals.
+
+    ``differentiable=True`` (with a discriminator built with it too): ``forward(y_hat, y)`` with a ``y_hat`` that requires grad runs
+    D(y) under no_grad and D(y_hat) with the graph, as the reference's generator step does (trainer/autoencoder.py:102-108);
+    ``adversarial_loss`` and ``feature_matching_loss`` then carry grad, ``real_loss`` and ``fake_loss`` are plain values, and all
+    four equal the forward-only call's.  That pass holds both feature pyramids until the losses are folded and the ``y_hat`` one
+    until backward.  ``y`` may never require grad; ``update()`` stays forward only."""
 
     def __init__(self, discriminator, generator_adv_loss_params=None, discriminator_adv_loss_params=None,
-                 use_feat_match_loss=True, feat_match_loss_params=None, lambda_adv=1.0, lambda_feat_match=2.0):
+                 use_feat_match_loss=True, feat_match_loss_params=None, lambda_adv=1.0, lambda_feat_match=2.0,
+                 differentiable=False):
         self.discriminator = discriminator
+        self.differentiable = bool(differentiable)
         self.gen_adv = GeneratorAdversarialLoss(**dict(generator_adv_loss_params or {}))
         self.dis_adv = DiscriminatorAdversarialLoss(**dict(discriminator_adv_loss_params or {}))
         self.feat_match = FeatureMatchLoss(**dict(feat_match_loss_params or {})) if use_feat_match_loss else None
@@ -640,8 +828,57 @@ class AdversarialEval:
         out["real_loss"], out["fake_loss"] = real, fake
         return out
 
+    def _forward_grad(self, dev, y_hat, y):
+        _no_grad_inputs(y)
+        y_hat, y = _settled(y_hat), _settled(y)
+        if tuple(y_hat.shape) != tuple(y.shape):
+            raise ValueError(f"y_hat {tuple(y_hat.shape)} and y {tuple(y.shape)} must have the same shape")
+        if y.dim() == 2:
+            y_hat, y = y_hat[:, None], y[:, None]
+        with torch.no_grad():
+            real = [_flat(t) for _, _, t, _ in self.discriminator.layers_of(y)]
+        hats, where = [], []
+        for d, l, t, n_layers in self.discriminator.layers_of(y_hat):
+            hats.append(t)
+            where.append((d, l, l == n_layers - 1))
+        flat = [_flat(t, True) for t in hats]
+        n_d, fm = self._layout()
+        fm_off = [3 * n_d + sum(fm[:d]) for d in range(n_d)]
+        gk, _ = self.gen_adv.kind()
+        (rk, _), (fk, _) = self.dis_adv.kinds()
+        used = [self.feat_match is not None and (not last or self.feat_match.include_final_outputs) for _, _, last in where]
+        plain = {}
+
+        def value():
+            terms = self._new_terms(dev)
+            for (d, l, last), a, b, fm_term in zip(where, flat, real, used):
+                if fm_term:
+                    terms.fold(fm_off[d] + l, a, LOSS_L1, b)
+                if last:
+                    terms.fold(3 * d, a, gk)
+                    terms.fold(3 * d + 1, b, rk)
+                    terms.fold(3 * d + 2, a, fk)
+            plain.update({k: v.to(torch.float32) for k, v in self._combine(terms.means()).items()})
+            return tuple(plain[k] for k in ("adversarial_loss", "feature_matching_loss") if k in plain)
+
+        fm_coefs = iter(self.feat_match.coefs([a.numel() for a, u in zip(flat, used) if u], fm)) if self.feat_match else None
+        terms = []
+        for i, ((d, l, last), a, b, fm_term) in enumerate(zip(where, flat, real, used)):
+            if fm_term:
+                terms.append((i, a, b, LOSS_L1, next(fm_coefs), {0: self.lambda_adv * self.lambda_feat_match, 1: 1.0}))
+            if last:
+                terms.append((i, a, None, gk, self.gen_adv.coef(a.numel(), n_d) * self.lambda_adv, {0: 1.0}))
+        out = _LossFn.apply(value, terms, *hats)
+        res = dict(plain)
+        res["adversarial_loss"] = out[0]
+        if self.feat_match is not None:
+            res["feature_matching_loss"] = out[1]
+        return res
+
     def forward(self, y_hat, y):
         dev = self.discriminator._prepare_device(y)
+        if _wants_grad(self.differentiable, y_hat):
+            return self._forward_grad(dev, y_hat, y)
         terms = self._new_terms(dev)
         self._fold(terms, y_hat, y)
         return {k: v.to(torch.float32) for k, v in self._combine(terms.means()).items()}
@@ -668,14 +905,15 @@ class AdversarialEval:
         return {k: float(v) for k, v in self._combine(self._totals.means()).items()}
 
 
-def from_config(config, discriminator):
+def from_config(config, discriminator, differentiable=False):
     """AdversarialEval with a training config's loss settings (codecTrain.py:190-201, trainer/trainerGAN.py:244-268)."""
     return AdversarialEval(discriminator,
                            generator_adv_loss_params=config.get("generator_adv_loss_params", {}),
                            discriminator_adv_loss_params=config.get("discriminator_adv_loss_params", {}),
                            use_feat_match_loss=config.get("use_feat_match_loss", False),
                            feat_match_loss_params=config.get("feat_match_loss_params", {}),
-                           lambda_adv=config.get("lambda_adv", 1.0), lambda_feat_match=config.get("lambda_feat_match", 1.0))
+                           lambda_adv=config.get("lambda_adv", 1.0), lambda_feat_match=config.get("lambda_feat_match", 1.0),
+                           differentiable=differentiable)
 
 
 def discriminator_for(model_type, discriminator_params, device=None):

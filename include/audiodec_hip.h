@@ -336,6 +336,34 @@ int adk_disc_loss(const float* a, const float* b, int64_t n, int32_t kind, doubl
                   float* loss, void* stream);
 
 /*
+ * HiFi-GAN discriminator backward to its input (the weights are constants), exact f32.  Every output element is written exactly
+ * once, by one thread or one accumulator, with no atomics: bitwise reproducible.
+ * adk_disc_conv_grad: the backward-data of adk_disc_conv with the same layer arguments:
+ *   dy, y [n_items][c_out][h_out][period]  ->  dx [n_items][c_in][h_in][period]
+ *   dx[i][g c_in/groups + ci][h][j] = sum over o of group g and taps t with (h + pad - t) % stride == 0 and
+ *     0 <= h' = (h + pad - t) / stride < h_out  of  W[o][ci][t] dy[i][o][h'][j] (act == 2 ? (y[i][o][h'][j] > 0 ? 1 : slope) : 1)
+ *   y is the layer's saved output (after the activation); read, and required, only when act == 2, which needs slope >= 0.
+ *   Rows of x the forward never read get zeros.
+ *   impl 1 (direct): w is the reference's layout [c_out][c_in/groups][kernel].
+ *   impl 2 (gemm):   w is [groups][phase r < stride][(o, tt)][c_in/groups]: for each group and each r the taps t = r + tt stride
+ *                    of every output channel o of the group, (o, tt) at o * taps(r) + tt; a K loop runs over one phase only.
+ * adk_disc_prep_grad: the backward of adk_disc_prep with the same (n_in, op, a, b, c); dy has the forward's output length:
+ *   op 0: dx[i] = dy[i] + dy[2 (n_in - 1) - i] where that index is in [n_in, n_in + a);
+ *   op 1: dx[t] = (sum of dy[i] over the windows i b - c <= t < i b - c + a) / a.
+ * adk_disc_loss_grad: grad[i] = c * d/da term(a[i], b[i]) for the kinds of adk_disc_loss:
+ *   0: 2 (a - 1)   1: 2 a   2: sign(a - b), sign(0) = 0   3: 1   4: a < 1 ? 1 : 0   5: a > -1 ? -1 : 0
+ *   c = (float)(coef * upstream[0]); upstream [1] f32 is read on the device.
+ * Every argument is checked before any HIP call (ADK_ERR_ARG).  No allocation, no synchronisation.
+ */
+int adk_disc_conv_grad(const float* dy, const float* y, const float* w, float* dx, int32_t n_items, int32_t c_in, int32_t h_in,
+                       int32_t period, int32_t c_out, int32_t groups, int32_t kernel, int32_t stride, int32_t pad, int32_t act,
+                       float slope, int32_t impl, void* stream);
+int adk_disc_prep_grad(const float* dy, float* dx, int32_t rows, int32_t n_in, int32_t op, int32_t a, int32_t b, int32_t c,
+                       void* stream);
+int adk_disc_loss_grad(const float* a, const float* b, int64_t n, int32_t kind, double coef, const float* upstream, float* grad,
+                       void* stream);
+
+/*
  * UnivNet spectral discriminator forward (models/vocoder/modules/discriminator.py:451-640), exact f32.  The period half of the
  * UnivNet discriminator is adk_disc_conv / adk_disc_prep, the loss sums are adk_disc_loss.
  * adk_spectrogram: torchaudio.functional.spectrogram(x, pad, window, n_fft, hop, win_length, power=1.0, normalized=False)
