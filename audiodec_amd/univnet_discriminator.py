@@ -14,9 +14,17 @@ State dicts use the reference's keys, including the persistent ``window`` buffer
 spectrogram uses the loaded window.  Weight norm (``weight_g``/``weight_v``) is folded once at load as
 ``torch._weight_norm(v, g, 0)``.
 
-Forward only: an input that requires grad while grad is enabled raises NotImplementedError.
+Forward only by default: an input that requires grad while grad is enabled raises NotImplementedError.  The classes above take
+no ``differentiable`` argument; the backward to the input arrives as subclasses with the same arguments and state-dict keys,
+``DifferentiableSpectralDiscriminator``, ``DifferentiableMultiResolutionSpectralDiscriminator`` and
+``DifferentiableDiscriminator`` (``discriminator_for`` / ``load_discriminator`` build them with ``differentiable=True``).  With an
+input that requires grad they give it a gradient through ``torch.autograd``: the spectrogram is a Function whose backward is
+adk_spectrogram_grad (a bin of magnitude 0 passes no gradient, as torch's ``abs``), each 2-D conv with its activation is
+``discriminator._ConvFn`` with adk_conv2d_grad behind it, and the period half is built with ``differentiable=True``.  The weights
+stay constants, the backward is once-differentiable and bitwise reproducible, and without grad wanted they run the plain forward.
 """
 import copy
+import functools
 from collections import namedtuple
 
 import torch
@@ -28,6 +36,7 @@ from .discriminator import (ACT_LEAKY, ACT_NONE, IMPL_DIRECT, IMPL_GEMM, MPD_DIS
                             effective_weight, expected_keys, from_config)
 
 GEMM_MAX_K = 4096                                     # adk_conv2d impl 2: c_in * kh * kw
+GRAD_GEMM_MAX_K = 4096                                # adk_conv2d_grad impl 2: c_out * kh * kw
 
 
 # one 2-D conv layer: kernel, stride, pad are (frames axis, bins axis); norm "none" | "weight"
@@ -103,11 +112,33 @@ def conv_impl(layer):
     return IMPL_DIRECT if layer.cin == 1 or layer.cout == 1 else IMPL_GEMM
 
 
+def pack_grad_weights2d(w, layer):
+    """The backward-data GEMM's weights of one spectral layer from its (C_out, C_in, kh, kw) weight: [phase][kk][m], phases
+    (rh, rw) with rh < stride_h major and rw < stride_w minor.  Phase (rh, rw) holds the taps th = rh, rh + stride_h, ... and
+    tw = rw, rw + stride_w, ... (the only ones that reach an input position with (h + pad_h) % stride_h == rh and
+    (w + pad_w) % stride_w == rw), kk = (co * taps(rh) + tth) * taps(rw) + ttw and m = ci.  Flat (C_out * kh * kw, C_in): the
+    phases follow each other, one without taps takes no rows."""
+    (kh, kw), (sh, sw) = layer.kernel, layer.stride
+    w = w.reshape(layer.cout, layer.cin, kh, kw)
+    phases = [w[:, :, rh::sh, rw::sw].permute(0, 2, 3, 1).reshape(-1, layer.cin)
+              for rh in range(min(sh, kh)) for rw in range(min(sw, kw))]
+    return torch.cat(phases, 0).contiguous()
+
+
+def _check_grad_layers(layers):
+    """What a differentiable spectral discriminator needs of its layers beyond discriminator._check_slopes."""
+    for L in layers:
+        kg = L.cout * L.kernel[0] * L.kernel[1]
+        if conv_impl(L) == IMPL_GEMM and kg > GRAD_GEMM_MAX_K:
+            raise NotImplementedError(f"{L.key}: C_out * kh * kw = {kg} is beyond the HIP 2-D conv backward's {GRAD_GEMM_MAX_K}")
+
+
 class _Conv2d:
     """One spectral layer's device weights."""
 
     def __init__(self, layer, w, b, dev):
         self.layer, self.impl = layer, conv_impl(layer)
+        self._w_grad = None                                                    # the backward's GEMM packing, made on first use
         kg = layer.cin * layer.kernel[0] * layer.kernel[1]
         if self.impl == IMPL_GEMM:
             if kg > GEMM_MAX_K:
@@ -115,6 +146,28 @@ class _Conv2d:
             w = w.reshape(layer.cout, kg).t()                                   # [cin * kh * kw][cout]
         self.w = w.contiguous().to(dev)
         self.b = b.float().contiguous().to(dev) if b is not None else None
+
+    def grad_weights(self):
+        """The weights adk_conv2d_grad reads: the reference's layout for the direct kernel, pack_grad_weights2d for the GEMM
+        (re-packed once, on the device, from the forward packing)."""
+        if self.impl != IMPL_GEMM:
+            return self.w
+        if self._w_grad is None:
+            L = self.layer
+            self._w_grad = pack_grad_weights2d(self.w.t().reshape(L.weight_shape), L)
+        return self._w_grad
+
+    def grad(self, dy, y, x_shape):
+        """dy, y (N, C_out, H', W') contiguous float32 -> dx of x_shape (N, C_in, H, W)."""
+        L = self.layer
+        n, cin, h, w = x_shape
+        dx = torch.empty(n, cin, h, w, dtype=torch.float32, device=dy.device)
+        act = ACT_LEAKY if L.act_slope is not None else ACT_NONE
+        native.check(native.lib().adk_conv2d_grad(_ptr(dy), _ptr(y) if act else None, _ptr(self.grad_weights()), _ptr(dx), n, cin, h,
+                                                  w, L.cout, L.kernel[0], L.kernel[1], L.stride[0], L.stride[1], L.pad[0], L.pad[1],
+                                                  act, float(L.act_slope or 0.0), self.impl, native.current_stream(dy.device)),
+                     "adk_conv2d_grad")
+        return dx
 
     def __call__(self, x):
         """x (N, C_in, H, W) contiguous float32 -> (N, C_out, H', W')."""
@@ -141,6 +194,33 @@ def spectrogram(x, window, fft_size, hop_size, win_length):
     native.check(native.lib().adk_spectrogram(_ptr(x), n, t, win_length // 2, fft_size, hop_size, _ptr(window), win_length,
                                               _ptr(out), native.current_stream(x.device)), "adk_spectrogram")
     return out
+
+
+class _SpecFn(torch.autograd.Function):
+    """spectrogram() with a backward to the signal: adk_spectrogram_grad on the saved input (the frames are recomputed)."""
+
+    @staticmethod
+    def forward(ctx, x, window, fft_size, hop_size, win_length):
+        ctx.args = (window, fft_size, hop_size, win_length)
+        ctx.save_for_backward(x)
+        return spectrogram(x, window, fft_size, hop_size, win_length)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        window, fft_size, hop_size, win_length = ctx.args
+        n, t = x.shape
+        g = g.to(torch.float32).contiguous()
+        lib = native.lib()
+        ws_bytes = int(lib.adk_spectrogram_grad_workspace_bytes(n, t, win_length // 2, fft_size, hop_size))
+        if ws_bytes < 0:
+            native.check(ws_bytes, "adk_spectrogram_grad_workspace_bytes")
+        ws = torch.empty(max(ws_bytes // 4, 1), dtype=torch.float32, device=x.device)
+        dx = torch.empty(n, t, dtype=torch.float32, device=x.device)
+        native.check(lib.adk_spectrogram_grad(_ptr(x), _ptr(g), n, t, win_length // 2, fft_size, hop_size, _ptr(window), win_length,
+                                              _ptr(ws), _ptr(dx), native.current_stream(x.device)), "adk_spectrogram_grad")
+        return dx, None, None, None, None
 
 
 def _window_shapes(specs):
@@ -202,16 +282,19 @@ class UnivNetSpectralDiscriminator(_Module):
             if x.shape[1] != 1:
                 raise ValueError(f"expected a (B, 1, T) input, got {tuple(x.shape)}")
             _check_length(x.shape[2], self._specs)
+        grad = D._wants_grad(getattr(self, "differentiable", False), x)
         b, _, t = x.shape
-        h = spectrogram(x.reshape(b, t), self._windows[self.window_key], self.fft_size, self.hop_size, self.win_length)
+        args = (x.reshape(b, t), self._windows[self.window_key], self.fft_size, self.hop_size, self.win_length)
+        h = _SpecFn.apply(*args) if grad else spectrogram(*args)
         h = h.reshape(b, 1, h.shape[1], h.shape[2])
         for l, L in enumerate(self.layers):
-            h = self._convs[L.key](h)
+            h = D._conv_op(self._convs[L.key], h, grad)
             yield d0, l, h, len(self.layers)
 
 
 class UnivNetMultiResolutionSpectralDiscriminator(_Module):
     """discriminator.py:585-640 on the HIP path.  Same arguments and defaults."""
+    _spectral_class = UnivNetSpectralDiscriminator
 
     def __init__(self, fft_sizes=[1024, 2048, 512], hop_sizes=[120, 240, 50], win_lengths=[600, 1200, 240], window="hann_window",
                  discriminator_params=MRSD_DISC_DEFAULTS, device=None, _prefix=""):
@@ -219,9 +302,8 @@ class UnivNetMultiResolutionSpectralDiscriminator(_Module):
         self.discriminators = []
         for i in range(len(fft_sizes)):
             params = copy.deepcopy(dict(discriminator_params))
-            self.discriminators.append(UnivNetSpectralDiscriminator(fft_size=fft_sizes[i], hop_size=hop_sizes[i],
-                                                                    win_length=win_lengths[i], window=window,
-                                                                    _prefix=f"{_prefix}discriminators.{i}.", **params))
+            self.discriminators.append(self._spectral_class(fft_size=fft_sizes[i], hop_size=hop_sizes[i], win_length=win_lengths[i],
+                                                            window=window, _prefix=f"{_prefix}discriminators.{i}.", **params))
         self.discriminator_layers = [d.layers for d in self.discriminators]
         self._specs = [s for d in self.discriminators for s in d._specs]
         self._init_layers([L for ls in self.discriminator_layers for L in ls], device, windows=_window_shapes(self._specs),
@@ -240,15 +322,17 @@ class UnivNetMultiResolutionSpectralDiscriminator(_Module):
 class Discriminator(_Module):
     """models/vocoder/UnivNet.py:23-103 on the HIP path: mrsd(x) + mpd(x).  Same arguments and defaults; state-dict keys
     ``mrsd.…`` (with the ``window`` buffers) and ``mpd.…`` as the reference's."""
+    _spectral_half_class = UnivNetMultiResolutionSpectralDiscriminator
+    _period_half_differentiable = False
 
     def __init__(self, fft_sizes=[1024, 2048, 512], hop_sizes=[120, 240, 50], win_lengths=[600, 1200, 240], window="hann_window",
                  spectral_discriminator_params=MRSD_DISC_DEFAULTS, periods=[2, 3, 5, 7, 11],
                  period_discriminator_params=MPD_DISC_DEFAULTS, flat_channel=False, device=None):
         self.flat_channel = bool(flat_channel)
-        self.mrsd = UnivNetMultiResolutionSpectralDiscriminator(fft_sizes=fft_sizes, hop_sizes=hop_sizes, win_lengths=win_lengths,
-                                                                window=window, discriminator_params=spectral_discriminator_params,
-                                                                _prefix="mrsd.")
-        self.mpd = D.HiFiGANMultiPeriodDiscriminator(periods=periods, discriminator_params=period_discriminator_params, _prefix="mpd.")
+        self.mrsd = self._spectral_half_class(fft_sizes=fft_sizes, hop_sizes=hop_sizes, win_lengths=win_lengths, window=window,
+                                              discriminator_params=spectral_discriminator_params, _prefix="mrsd.")
+        self.mpd = D.HiFiGANMultiPeriodDiscriminator(periods=periods, discriminator_params=period_discriminator_params,
+                                                     differentiable=self._period_half_differentiable, _prefix="mpd.")
         self.discriminator_layers = self.mrsd.discriminator_layers + self.mpd.discriminator_layers
         self._specs = self.mrsd._specs
         self._init_layers(self.mrsd._layers + self.mpd._layers, device, windows=_window_shapes(self._specs),
@@ -259,7 +343,8 @@ class Discriminator(_Module):
         return len(self.discriminator_layers)
 
     def layers_of(self, x):
-        D._no_grad_inputs(x)
+        if not D._wants_grad(getattr(self, "differentiable", False), x):
+            D._no_grad_inputs(x)
         if isinstance(x, torch.Tensor) and x.dim() == 3:          # both checks before any launch
             if x.shape[1] != 1 and not self.flat_channel:
                 raise ValueError(f"input with {x.shape[1]} channels and flat_channel=False: the reference fails inside its first "
@@ -273,13 +358,48 @@ class Discriminator(_Module):
         yield from self.mpd.layers_of(x, len(self.mrsd.discriminator_layers), prepared=True)
 
 
-def discriminator_for(model_type, discriminator_params, device=None):
-    """codecTrain.py:140-147: the UnivNet discriminator for symAudioDecUniv / UnivNet, the HiFi-GAN one for symAudioDec / HiFiGAN."""
+class DifferentiableSpectralDiscriminator(UnivNetSpectralDiscriminator):
+    """UnivNetSpectralDiscriminator with a backward to its input (module docstring).  Same arguments and state-dict keys."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        D._check_slopes(self.layers, True)
+        _check_grad_layers(self.layers)
+        self.differentiable = True
+
+
+class DifferentiableMultiResolutionSpectralDiscriminator(UnivNetMultiResolutionSpectralDiscriminator):
+    """UnivNetMultiResolutionSpectralDiscriminator of DifferentiableSpectralDiscriminator children."""
+    _spectral_class = DifferentiableSpectralDiscriminator
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.differentiable = True
+
+
+class DifferentiableDiscriminator(Discriminator):
+    """Discriminator with a backward to its input: differentiable spectral children and a period half built with
+    ``differentiable=True``.  With ``flat_channel=True`` a (B, C, T) input gets a (B, C, T) gradient."""
+    _spectral_half_class = DifferentiableMultiResolutionSpectralDiscriminator
+    _period_half_differentiable = True
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.differentiable = True
+
+
+def discriminator_for(model_type, discriminator_params, device=None, differentiable=False):
+    """codecTrain.py:140-147: the UnivNet discriminator for symAudioDecUniv / UnivNet, the HiFi-GAN one for symAudioDec / HiFiGAN;
+    with ``differentiable=True`` the ones with a backward to their input."""
     if model_type in ("symAudioDecUniv", "UnivNet"):
-        return Discriminator(**dict(discriminator_params or {}), device=device)
+        cls = DifferentiableDiscriminator if differentiable else Discriminator
+        return cls(**dict(discriminator_params or {}), device=device)
+    if differentiable and model_type in ("symAudioDec", "HiFiGAN"):
+        return D.Discriminator(**dict(discriminator_params or {}), device=device, differentiable=True)
     return D.discriminator_for(model_type, discriminator_params, device=device)
 
 
-def load_discriminator(checkpoint, device=None):
+def load_discriminator(checkpoint, device=None, differentiable=False):
     """discriminator.load_discriminator for a training checkpoint of any of the four model types."""
-    return D.load_discriminator(checkpoint, device, discriminator_for)
+    build = functools.partial(discriminator_for, differentiable=True) if differentiable else discriminator_for
+    return D.load_discriminator(checkpoint, device, build)

@@ -390,6 +390,38 @@ int adk_conv2d(const float* x, const float* w, const float* bias, float* y, int3
                float slope, int32_t impl, void* stream);
 
 /*
+ * UnivNet spectral discriminator backward to its input (the weights are constants), exact f32.  Every output element is written
+ * exactly once, by one thread or one accumulator, with no atomics: bitwise reproducible.  The period half's backward is
+ * adk_disc_conv_grad / adk_disc_prep_grad, the losses' is adk_disc_loss_grad.
+ * adk_conv2d_grad: the backward-data of adk_conv2d with the same layer arguments:
+ *   dy, y [n_items][c_out][h_out][w_out]  ->  dx [n_items][c_in][h_in][w_in]
+ *   dx[i][ci][h][w] = sum over o and taps (th, tw) with (h + ph - th) % sh == 0, (w + pw - tw) % sw == 0,
+ *     0 <= h' = (h + ph - th) / sh < h_out, 0 <= w' = (w + pw - tw) / sw < w_out
+ *     of  W[o][ci][th][tw] dy[i][o][h'][w'] (act == 2 ? (y[i][o][h'][w'] > 0 ? 1 : slope) : 1)
+ *   y is the layer's saved output (after the activation); read, and required, only when act == 2, which needs slope >= 0.
+ *   Rows and columns of x the forward never read get zeros.
+ *   impl 1 (direct): w is the reference's [c_out][c_in][kh][kw]; any layer shape, meant for c_in = 1 or c_out = 1.
+ *   impl 2 (gemm):   w is [phase (rh, rw), rh major][(o, tth, ttw)][c_in]: for each phase rh < sh, rw < sw the taps
+ *                    th = rh + tth sh, tw = rw + ttw sw of every output channel o, (o, tth, ttw) at
+ *                    (o * taps(rh) + tth) * taps(rw) + ttw; a K loop runs over one phase only.  c_out * kh * kw <= 4096.
+ * adk_spectrogram_grad: the vector-Jacobian product of adk_spectrogram with respect to x.  The arguments shared with
+ *   adk_spectrogram mean the same and have the same limits; g [n_signals][frames][n_fft/2 + 1] f32 is the gradient of its out,
+ *   grad_x [n_signals][n_samples] f32 = sum over out of g d out / d x, as torch's autograd defines it: a bin with |X| == 0
+ *   passes no gradient (abs backward, sgn(0) = 0) -- every bin of a frame that lies in the zero padding is one.
+ *   Each frame's forward is recomputed; its windowed gradient goes to workspace [n_signals][frames][n_fft] f32 =
+ *   adk_spectrogram_grad_workspace_bytes(n_signals, n_samples, pad, n_fft, hop) bytes, 4-byte aligned, any contents; a second
+ *   launch gathers every sample's contributions through both paddings in ascending frame order.  grad_x is fully written (a
+ *   sample no frame reaches gets 0).  n_signals == 0 is a no-op.
+ * Every argument is checked before any HIP call (ADK_ERR_ARG / ADK_ERR_SHAPE).  No allocation, no synchronisation.
+ */
+int adk_conv2d_grad(const float* dy, const float* y, const float* w, float* dx, int32_t n_items, int32_t c_in, int32_t h_in,
+                    int32_t w_in, int32_t c_out, int32_t kh, int32_t kw, int32_t sh, int32_t sw, int32_t ph, int32_t pw, int32_t act,
+                    float slope, int32_t impl, void* stream);
+int64_t adk_spectrogram_grad_workspace_bytes(int32_t n_signals, int32_t n_samples, int32_t pad, int32_t n_fft, int32_t hop);
+int adk_spectrogram_grad(const float* x, const float* g, int32_t n_signals, int32_t n_samples, int32_t pad, int32_t n_fft,
+                         int32_t hop, const float* window, int32_t win_length, void* workspace, float* grad_x, void* stream);
+
+/*
  * Multi-resolution STFT loss and waveform-shape loss, one resolution / one window length per call (losses/stft_loss.py:19-170,
  * losses/waveform_loss.py:15-75).  The STFT is adk_logmel's: torch.stft's defaults, the window [win_length] centred in n_fft,
  * 1 + n_samples/hop frames, n_fft/2 + 1 bins, mag = sqrt(max(re^2 + im^2, eps)) (a NaN stays NaN).

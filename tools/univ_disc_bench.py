@@ -7,12 +7,18 @@ torch.stft / F.conv2d (MIOpen) in f32, then the reference's loss formulas with t
 process after warm-up and are timed with device events.  Prints one JSON line: the median ms of each leg, the spread of the
 torch leg, and per-layer FLOPs of the spectral half for reading a rocprofv3 kernel trace against.
 
-    python tools/univ_disc_bench.py [--batch 16] [--samples 48000] [--iters 7] [--hip-only]
+``--backward`` times one generator step's GAN part instead (trainer/autoencoder.py:102-108): D(y) under no_grad, D(y_hat) with the
+graph, adversarial_loss, and its backward to y_hat.  HIP: AdversarialEval(differentiable=True) on a DifferentiableDiscriminator
+(adk_spectrogram_grad, adk_conv2d_grad, adk_disc_conv_grad and friends).  torch: autograd through the same composition.  After a
+warm-up the two legs alternate, each call ending in a device synchronise; the JSON line has each leg's median and min / max.
+
+    python tools/univ_disc_bench.py [--batch 16] [--samples 48000] [--iters 7] [--hip-only] [--backward]
 """
 import argparse
 import json
 import os
 import sys
+import time
 
 import torch
 import torch.nn.functional as F
@@ -22,9 +28,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 
 
-def torch_pass(d, ws, x, cfg):
-    """The reference's forward and losses with torch ops: (adv, fm, real, fake) as 0-d tensors."""
-    n = x.shape[0] // 2
+def torch_features(d, ws, x):
+    """The reference's forward with torch ops: the list (per sub-discriminator) of lists of feature maps."""
     outs = []
     for sub in d.mrsd.discriminators:
         pad = sub.win_length // 2
@@ -53,11 +58,71 @@ def torch_pass(d, ws, x, cfg):
             o.append(h)
         o[-1] = o[-1].flatten(1)
         outs.append(o)
+    return outs
+
+
+def torch_pass(d, ws, x, cfg):
+    """The reference's forward and losses with torch ops: (adv, fm, real, fake) as 0-d tensors."""
+    n = x.shape[0] // 2
+    outs = torch_features(d, ws, x)
     adv = sum(F.mse_loss(o[-1][:n], torch.ones_like(o[-1][:n])) for o in outs)
     fm = sum(sum(F.l1_loss(t[:n], t[n:]) for t in o[:-1]) for o in outs)
     real = sum(F.mse_loss(o[-1][n:], torch.ones_like(o[-1][n:])) for o in outs)
     fake = sum(F.mse_loss(o[-1][:n], torch.zeros_like(o[-1][:n])) for o in outs)
     return cfg["lambda_adv"] * (adv + cfg["lambda_feat_match"] * fm), fm, real, fake
+
+
+def torch_step(d, ws, y_hat, y, cfg):
+    """The generator step's GAN part with torch autograd: (adversarial_loss, its gradient with respect to y_hat)."""
+    a = y_hat.detach().requires_grad_(True)
+    with torch.no_grad():
+        p = torch_features(d, ws, y)
+    p_ = torch_features(d, ws, a)
+    adv = sum(F.mse_loss(o[-1], torch.ones_like(o[-1])) for o in p_)
+    fm = sum(sum(F.l1_loss(t, u) for t, u in zip(oh[:-1], o[:-1])) for oh, o in zip(p_, p))
+    loss = cfg["lambda_adv"] * (adv + cfg["lambda_feat_match"] * fm)
+    loss.backward()
+    return loss.detach(), a.grad
+
+
+def hip_step(ev, y_hat, y):
+    a = y_hat.detach().requires_grad_(True)
+    loss = ev(a, y)["adversarial_loss"]
+    loss.backward()
+    return loss.detach(), a.grad
+
+
+def backward_bench(a, sd, ws, cfg, y_hat, y, dev):
+    import univ_disc_oracle as UO
+    from audiodec_amd import univnet_discriminator as U
+    d = U.DifferentiableDiscriminator(**UO.PARAMS["v3"], device=dev).load_state_dict(sd)
+    ev = U.from_config(cfg, d, differentiable=True)
+    steps = {"hip": lambda: hip_step(ev, y_hat, y)}
+    if not a.hip_only:
+        steps["torch"] = lambda: torch_step(d, ws, y_hat, y, cfg)
+    res, ts = {}, {k: [] for k in steps}
+    for k, fn in steps.items():                     # warm-up: code objects, MIOpen's algorithm choice, the backward weight packing
+        for _ in range(2):
+            res[k] = fn()
+        torch.cuda.synchronize()
+    for _ in range(a.iters):                        # alternate, so that drift of the shared host hits both alike
+        for k, fn in steps.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            res[k] = fn()
+            torch.cuda.synchronize()
+            ts[k].append((time.perf_counter() - t0) * 1e3)
+    med = {k: sorted(v)[len(v) // 2] for k, v in ts.items()}
+    out = {"mode": "backward", "batch": a.batch, "samples": a.samples, "iters": a.iters, "hip_ms": round(med["hip"], 3),
+           "hip_ms_min_max": [round(min(ts["hip"]), 3), round(max(ts["hip"]), 3)], "loss": {"hip": float(res["hip"][0])},
+           "grad_finite": bool(torch.isfinite(res["hip"][1]).all())}
+    if not a.hip_only:
+        gh, gt = res["hip"][1], res["torch"][1]
+        out.update({"torch_ms": round(med["torch"], 3), "torch_ms_min_max": [round(min(ts["torch"]), 3), round(max(ts["torch"]), 3)],
+                    "torch_spread_ms": round(max(ts["torch"]) - min(ts["torch"]), 3), "speedup": round(med["torch"] / med["hip"], 3),
+                    "grad_max_abs": float(gt.abs().max()), "grad_max_diff": float((gh - gt).abs().max())})
+        out["loss"]["torch"] = float(res["torch"][0])
+    return out
 
 
 def spectral_flops(d, t):
@@ -78,6 +143,7 @@ def main():
     ap.add_argument("--samples", type=int, default=48000)
     ap.add_argument("--iters", type=int, default=7)
     ap.add_argument("--hip-only", action="store_true", help="run only the HIP leg (for a kernel trace of its own)")
+    ap.add_argument("--backward", action="store_true", help="time forward + backward of adversarial_loss to y_hat")
     a = ap.parse_args()
     import univ_disc_oracle as UO
     from audiodec_amd import univnet_discriminator as U
@@ -94,6 +160,9 @@ def main():
     g = torch.Generator(device=dev).manual_seed(0)
     y = (0.1 * torch.randn(a.batch, 1, a.samples, device=dev, generator=g)).contiguous()
     y_hat = (y + 0.02 * torch.randn(a.batch, 1, a.samples, device=dev, generator=g)).contiguous()
+    if a.backward:
+        print(json.dumps(backward_bench(a, sd, ws, cfg, y_hat, y, dev)))
+        return
     x = torch.cat([y_hat, y])
 
     def timed(fn):
