@@ -5,12 +5,23 @@
 #include <string>
 #include <algorithm>
 #include <cstring>
+#include <initializer_list>
 #include "../../include/audiodec_hip.h"
 
 namespace adk {
 
 void set_error(const std::string& msg);
 int fail(int code, const std::string& msg);
+
+// An entry point's pointer checks, f its name: `missing` says that a pointer the call needs is null; then every pointer of
+// `ptrs` (named `names` in the message) must be 4-byte aligned.
+inline int check_pointers(const std::string& f, const char* names, bool missing, std::initializer_list<const void*> ptrs) {
+    if (missing) return fail(ADK_ERR_ARG, f + ": null pointer");
+    uintptr_t bits = 0;
+    for (const void* p : ptrs) bits |= reinterpret_cast<uintptr_t>(p);
+    if (bits & 3) return fail(ADK_ERR_ARG, f + ": " + names + " must be 4-byte aligned");
+    return ADK_OK;
+}
 
 #define ADK_HIP_CHECK(expr)                                                                   \
     do {                                                                                      \

@@ -1,4 +1,6 @@
-// The exact-f32 implicit-GEMM core of the discriminator convs (disc.hip's disc_gemm_kernel, univ_disc.hip's conv2d_gemm_kernel):
+// The exact-f32 implicit-GEMM core of the discriminator convs, forward and backward to the input (disc.hip's disc_gemm_kernel and
+// disc_gemm_grad_kernel, univ_disc.hip's conv2d_gemm_kernel and conv2d_gemm_grad_kernel), and what else the two families share:
+// the argument structs' pointers, the activation and its mask, the phase split of a strided backward, and the check of act / impl.
 //   Y[m][n] = bias[m] + sum_kk W[kk][m] X[kk][n]   on v_mfma_f32_32x32x2_f32 (f32 in, f32 accumulate: a k-ordered fmaf chain,
 //   no split precision), then LeakyReLU.
 // Workgroup tile BM x BN x 16 of 4 waves, WM x WN waves each holding TM x TN tiles of 32 x 32.  The 16-deep K slice of W
@@ -28,6 +30,44 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __device__ __forceinline__ float cg_act(float v, int act, float slope) {
     return (act == CG_ACT_LEAKY && v < 0.f) ? v * slope : v;
+}
+
+// The pointers of a conv's argument struct, which is one of these and the family's geometry.
+struct CgForwardPtrs {
+    const float* x;
+    const float* w;
+    const float* bias;                              // [c_out] or null
+    float* y;
+};
+struct CgBackwardPtrs {
+    const float* dy;
+    const float* y;                                 // of dy's shape: the forward's output (read when act is leaky)
+    const float* w;
+    float* dx;
+};
+
+// dz at idx of a layer's output: dy through the activation's mask, taken from the saved post-activation output y (y > 0 exactly
+// where the pre-activation is, for slope >= 0).
+__device__ __forceinline__ float cg_dz(const float* dy, const float* y, int act, float slope, long long idx) {
+    const float v = dy[idx];
+    return (act == CG_ACT_LEAKY && !(y[idx] > 0.f)) ? v * slope : v;
+}
+
+// One axis of a strided backward's phase split (kernel k, stride s, phase r = (index + pad) % s): taps r, r + s, ... < k of
+// phase r; the taps of the phases before r; the first input index of phase r; how many of n input indices first, first + s, ...
+// there are.
+__host__ __device__ inline int phase_taps(int k, int s, int r) { return r < k ? (k - r + s - 1) / s : 0; }
+__host__ __device__ inline int phase_taps_before(int k, int s, int r) { return (k / s) * r + (k % s < r ? k % s : r); }
+__host__ __device__ inline int phase_first(int pad, int s, int r) { return ((r - pad) % s + s) % s; }
+__host__ __device__ inline int phase_count(int n, int s, int first) { return first < n ? (n - first + s - 1) / s : 0; }
+
+// The check of act and impl both conv families' entry points make, f the entry point's name; `masked`: also slope >= 0 for a leaky layer (the backward, whose mask is cg_dz's).
+static inline int cg_check_act_impl(const std::string& f, int act, float slope, int impl, bool masked) {
+    if (act != CG_ACT_NONE && act != CG_ACT_LEAKY) return fail(ADK_ERR_ARG, f + ": act must be 0 (none) or 2 (leaky)");
+    if (masked && act == CG_ACT_LEAKY && !(slope >= 0.f))
+        return fail(ADK_ERR_ARG, f + ": the mask is taken from the output, which needs slope >= 0");
+    if (impl != CG_IMPL_DIRECT && impl != CG_IMPL_GEMM) return fail(ADK_ERR_ARG, f + ": impl must be 1 (direct) or 2 (gemm)");
+    return ADK_OK;
 }
 
 template <int WM, int WN, int TM, int TN, class Src>

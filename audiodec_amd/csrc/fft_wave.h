@@ -1,5 +1,5 @@
 // The one-wave real FFT shared by mel.hip (log-mel and its backward), stft_loss.hip (STFT magnitudes), both through
-// stft_frame.h, and univ_disc.hip (magnitude spectrogram).
+// stft_frame.h, and univ_disc.hip (magnitude spectrogram and its backward).
 // A frame of NFFT = 2 << LOG2N real samples lives in LDS as N = NFFT / 2 complex values and never leaves its wave: an N-point
 // complex radix-2 decimation-in-frequency FFT (natural order in, bit-reversed order out) plus the even/odd untangle that reads
 // the result back through the bit reversal.  Twiddles are exp(-2 pi i k / NFFT), k <= N, evaluated in f64 and rounded to f32.

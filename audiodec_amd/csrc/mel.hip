@@ -293,7 +293,7 @@ static int mel_grad(const char* fn, const float* xa, const float* xb, const floa
         launch_grad_frames<decltype(L)::value>(xa, xb, g, scale, upstream, n_signals, a, ga, slab, s);
     });
     ADK_HIP_CHECK(hipGetLastError());
-    launch_frame_grad_gather(slab, n_signals, n_samples, n_fft, hop, a.frames, grad, s);
+    launch_frame_grad_gather(slab, n_signals, n_samples, 0, n_fft, hop, a.frames, grad, s);
     ADK_HIP_CHECK(hipGetLastError());
     return ADK_OK;
 }

@@ -1,4 +1,4 @@
-// The tail every backward of a one-wave frame kernel ends in (mel.hip, stft_loss.hip): from the per-bin gradients of a frame's
+// The tail every backward of a one-wave frame kernel ends in (mel.hip, stft_loss.hip, univ_disc.hip): from the per-bin gradients of a frame's
 // spectrum to the gradient of the signal.
 //   frame_grad_tail:  (g_re, g_im) of bins k <= n_fft/2 in keep[] -> transposed untangle -> transposed FFT (fft_wave.h) -> the
 //                     centred window -> the frame's n_fft windowed gradients, one row of a slab [n_signals][frames][n_fft]
@@ -33,21 +33,23 @@ __device__ __forceinline__ void frame_grad_tail(const StftFrameArgs& a, float* b
 
 __device__ __forceinline__ long long floor_div(long long v, long long d) { return v >= 0 ? v / d : -((-v + d - 1) / d); }
 
-// The overlap-add through the reflect padding, gathered: sample t of a signal is padded position u = t, and also u = -t (t >= 1)
-// and u = 2 (T - 1) - t (t <= T - 2) where a frame reaches them; position u is float u - (f hop - n_fft/2) of frame f.  Frames in
-// ascending order, positions in ascending order within a frame; a sample no frame reaches gets 0.
+// The overlap-add through the reflect padding, gathered.  The frames were cut from the signal with `pad` zeros on both sides
+// (0 for torch.stft, univ_disc.hip's spectrogram pads), of length tp = T + 2 pad: sample t is its position p = t + pad, reached at
+// u = p and, through the reflect padding of that longer signal, at u = -p (p >= 1) and u = 2 (tp - 1) - p (p <= tp - 2) where a
+// frame reaches them; position u is float u - (f hop - n_fft/2) of frame f.  Frames in ascending order, positions in ascending
+// order within a frame; a sample no frame reaches gets 0.
 constexpr int GRAD_GATHER_THREADS = 256;
 constexpr int GRAD_GATHER_MAX_WG = 32768;
 static __global__ __launch_bounds__(GRAD_GATHER_THREADS) void frame_grad_gather_kernel(const float* __restrict__ slab,
-                                                                                       int n_signals, int T, int n_fft, int hop,
-                                                                                       long long frames,
+                                                                                       int n_signals, int T, int pad, int n_fft,
+                                                                                       int hop, long long frames,
                                                                                        float* __restrict__ grad_x) {
-    const long long total = (long long)n_signals * T, half = n_fft / 2;
+    const long long total = (long long)n_signals * T, half = n_fft / 2, tp = (long long)T + 2LL * pad;
     for (long long e = (long long)blockIdx.x * GRAD_GATHER_THREADS + threadIdx.x; e < total;
          e += (long long)gridDim.x * GRAD_GATHER_THREADS) {
-        const long long s = e / T, t = e - s * T;
-        const long long u[3] = {-t, t, 2LL * (T - 1) - t};
-        const bool on[3] = {t >= 1, true, t <= T - 2};
+        const long long s = e / T, p = e - s * T + pad;
+        const long long u[3] = {-p, p, 2LL * (tp - 1) - p};
+        const bool on[3] = {p >= 1, true, p <= tp - 2};
         long long lo = frames, hi = -1;
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
@@ -70,12 +72,12 @@ static __global__ __launch_bounds__(GRAD_GATHER_THREADS) void frame_grad_gather_
 }
 
 // The gather launch over slab [n_signals][frames][n_fft] into grad [n_signals][n_samples].
-static inline void launch_frame_grad_gather(const float* slab, int n_signals, int n_samples, int n_fft, int hop, long long frames,
-                                            float* grad, hipStream_t s) {
+static inline void launch_frame_grad_gather(const float* slab, int n_signals, int n_samples, int pad, int n_fft, int hop,
+                                            long long frames, float* grad, hipStream_t s) {
     const long long total = (long long)n_signals * n_samples;
     const int n_wg = (int)std::min<long long>((total + GRAD_GATHER_THREADS - 1) / GRAD_GATHER_THREADS, GRAD_GATHER_MAX_WG);
-    hipLaunchKernelGGL(frame_grad_gather_kernel, dim3(n_wg), dim3(GRAD_GATHER_THREADS), 0, s, slab, n_signals, n_samples, n_fft, hop,
-                       frames, grad);
+    hipLaunchKernelGGL(frame_grad_gather_kernel, dim3(n_wg), dim3(GRAD_GATHER_THREADS), 0, s, slab, n_signals, n_samples, pad, n_fft,
+                       hop, frames, grad);
 }
 
 }  // namespace adk

@@ -336,7 +336,7 @@ static int stft_grad(const char* fn, bool dist, const float* x, const float* y, 
         launch_stft_grad_frames<decltype(L)::value>(x, dist ? y : nullptr, g, sums, scale_sc, up_sc, scale_mag, up_mag, n_signals, a, slab, s);
     });
     ADK_HIP_CHECK(hipGetLastError());
-    launch_frame_grad_gather(slab, n_signals, n_samples, n_fft, hop, a.frames, grad, s);
+    launch_frame_grad_gather(slab, n_signals, n_samples, 0, n_fft, hop, a.frames, grad, s);
     ADK_HIP_CHECK(hipGetLastError());
     return ADK_OK;
 }

@@ -25,13 +25,13 @@ the ``y_hat`` feature pyramid alive until backward (the leaky masks are taken fr
 ``DiscriminatorAdversarialLoss`` and ``AdversarialEval.update`` stay forward only.
 """
 import copy
-import ctypes as C
 import os
 from collections import namedtuple
 
 import torch
 
 from . import lazy_guard, native
+from .loss_common import _ptr, _settled
 
 ACT_NONE, ACT_LEAKY = 0, 2
 IMPL_DIRECT, IMPL_GEMM = 1, 2
@@ -170,17 +170,6 @@ def expected_keys(layer):
     return ks + ([f"{k}.bias"] if layer.bias else [])
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _settled(t):
-    lg = lazy_guard.log_of(t)
-    if lg is not None:
-        lg.settle()
-    return lazy_guard.plain(t)
-
-
 def _no_grad_inputs(*ts):
     if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in ts):
         raise NotImplementedError("the HIP discriminator is forward only: run it under torch.no_grad() or detach the inputs")
@@ -206,54 +195,73 @@ def _check_slopes(layers, differentiable):
         raise ValueError("differentiable=True needs negative_slope >= 0: the backward takes the LeakyReLU mask from the layer's output")
 
 
-class _Conv:
-    """One layer's device weights."""
+class _ConvBase:
+    """One layer's device weights and its two native calls.  A subclass names the calls (``_native``: forward, backward) and
+    gives ``_impl``, the forward GEMM packing and its inverse (``_pack``, ``_unpack``), the backward GEMM packing
+    (``_pack_grad``), ``_out_shape`` and ``_geometry``, the integer arguments both calls take between the input's shape and
+    ``act``."""
 
     def __init__(self, layer, w, b, dev):
-        self.layer, self.impl = layer, conv_impl(layer)
+        self.layer, self.impl = layer, self._impl(layer)
+        act = ACT_LEAKY if layer.act_slope is not None else ACT_NONE
+        self._tail = (*self._geometry(), act, float(layer.act_slope or 0.0))   # between the shape and impl in both calls
         self._w_grad = None                                                    # the backward's GEMM packing, made on first use
         if self.impl == IMPL_GEMM:
-            g = layer.groups
-            w = w.reshape(g, layer.cout // g, -1).permute(0, 2, 1)             # [g][cin_g * k][cout_g]
+            w = self._pack(w)
         self.w = w.contiguous().to(dev)
         self.b = b.float().contiguous().to(dev) if b is not None else None
 
     def grad_weights(self):
-        """The weights adk_disc_conv_grad reads: the reference's layout for the direct kernel, pack_grad_weights for the GEMM
-        (re-packed once, on the device, from the forward packing)."""
+        """The weights the backward reads: the reference's layout for the direct kernel, ``_pack_grad`` for the GEMM (re-packed
+        once, on the device, from the forward packing)."""
         if self.impl != IMPL_GEMM:
             return self.w
         if self._w_grad is None:
-            L = self.layer
-            w = self.w.permute(0, 2, 1).reshape(L.cout, L.cin // L.groups, L.kernel)
-            self._w_grad = pack_grad_weights(w, L)
+            self._w_grad = self._pack_grad(self._unpack(self.w), self.layer)
         return self._w_grad
 
+    def _call(self, name, p0, p1, p2, out, x_shape):
+        """The native call ``name`` on its three input tensors (None for an absent one) and ``out``, for a layer input of x_shape."""
+        native.check(getattr(native.lib(), name)(_ptr(p0), _ptr(p1), _ptr(p2), _ptr(out), *x_shape, *self._tail, self.impl,
+                                                 native.current_stream(out.device)), name)
+        return out
+
     def grad(self, dy, y, x_shape):
-        """dy, y (N, C_out, H', P) contiguous float32 -> dx of x_shape (N, C_in, H, P)."""
-        L = self.layer
-        n, cin, h, p = x_shape
-        dx = torch.empty(n, cin, h, p, dtype=torch.float32, device=dy.device)
-        act = ACT_LEAKY if L.act_slope is not None else ACT_NONE
-        native.check(native.lib().adk_disc_conv_grad(_ptr(dy), _ptr(y) if act else None, _ptr(self.grad_weights()), _ptr(dx), n, cin,
-                                                      h, p, L.cout, L.groups, L.kernel, L.stride, L.pad, act,
-                                                      float(L.act_slope or 0.0), self.impl, native.current_stream(dy.device)),
-                     "adk_disc_conv_grad")
-        return dx
+        """dy, y of the output's shape, contiguous float32 -> dx of x_shape."""
+        dx = torch.empty(*x_shape, dtype=torch.float32, device=dy.device)
+        return self._call(self._native[1], dy, y if self.layer.act_slope is not None else None, self.grad_weights(), dx, x_shape)
 
     def __call__(self, x):
-        """x (N, C_in, H, P) contiguous float32 -> (N, C_out, H', P)."""
+        """x (N, C_in, ...) contiguous float32 -> (N, C_out, ...)."""
+        y = torch.empty(*self._out_shape(x.shape), dtype=torch.float32, device=x.device)
+        return self._call(self._native[0], x, self.w, self.b, y, x.shape)
+
+
+class _Conv(_ConvBase):
+    """One HiFi-GAN layer on (N, C, H, P)."""
+    _native = ("adk_disc_conv", "adk_disc_conv_grad")
+    _impl = staticmethod(conv_impl)
+    _pack_grad = staticmethod(pack_grad_weights)
+
+    def _pack(self, w):
+        g = self.layer.groups
+        return w.reshape(g, self.layer.cout // g, -1).permute(0, 2, 1)         # [g][cin_g * k][cout_g]
+
+    def _unpack(self, w):
         L = self.layer
-        n, cin, h, p = x.shape
+        return w.permute(0, 2, 1).reshape(L.cout, L.cin // L.groups, L.kernel)
+
+    def _out_shape(self, x_shape):
+        L = self.layer
+        n, _, h, p = x_shape
         ho = conv_out_len(h, L)
         if ho < 1:
             raise ValueError(f"{L.key}: input length {h} is shorter than the kernel {L.kernel} with padding {L.pad}")
-        y = torch.empty(n, L.cout, ho, p, dtype=torch.float32, device=x.device)
-        act = ACT_LEAKY if L.act_slope is not None else ACT_NONE
-        native.check(native.lib().adk_disc_conv(_ptr(x), _ptr(self.w), _ptr(self.b), _ptr(y), n, cin, h, p, L.cout, L.groups,
-                                                 L.kernel, L.stride, L.pad, act, float(L.act_slope or 0.0), self.impl,
-                                                 native.current_stream(x.device)), "adk_disc_conv")
-        return y
+        return n, L.cout, ho, p
+
+    def _geometry(self):
+        L = self.layer
+        return L.cout, L.groups, L.kernel, L.stride, L.pad
 
 
 def _prep(x, rows, n_in, op, a, b=0, c=0, n_out=None):
@@ -787,27 +795,45 @@ class AdversarialEval:
         n_d, fm = self._layout()
         return _Terms(3 * n_d + sum(fm), dev)
 
-    def _fold(self, terms, y_hat, y):
-        _no_grad_inputs(y_hat, y)
+    @staticmethod
+    def _waveforms(y_hat, y):
+        """Both settled and of one shape, (B, T) read as (B, 1, T)."""
         y_hat, y = _settled(y_hat), _settled(y)
         if tuple(y_hat.shape) != tuple(y.shape):
             raise ValueError(f"y_hat {tuple(y_hat.shape)} and y {tuple(y.shape)} must have the same shape")
         if y.dim() == 2:
             y_hat, y = y_hat[:, None], y[:, None]
-        x = torch.cat([y_hat.to(terms.sum.device, torch.float32), y.to(terms.sum.device, torch.float32)], 0)
+        return y_hat, y
+
+    def _fm_used(self, last):
+        return self.feat_match is not None and (not last or self.feat_match.include_final_outputs)
+
+    def _plan(self):
+        """Where the terms of a pass go and of which kind they are, once per pass: (the first feature-matching term of each
+        sub-discriminator, the generator's kind, the real and fake kinds)."""
         n_d, fm = self._layout()
-        fm_off = [3 * n_d + sum(fm[:d]) for d in range(n_d)]
-        gk, _ = self.gen_adv.kind()
         (rk, _), (fk, _) = self.dis_adv.kinds()
+        return [3 * n_d + sum(fm[:d]) for d in range(n_d)], self.gen_adv.kind()[0], rk, fk
+
+    def _fold_layer(self, terms, plan, d, l, last, a, b, n=None):
+        """Folds layer l of sub-discriminator d: the first n elements of a (the y_hat side) and b (the y side) into its
+        feature-matching term and, for the final output, the three adversarial terms."""
+        fm_off, gk, rk, fk = plan
+        if self._fm_used(last):
+            terms.fold(fm_off[d] + l, a, LOSS_L1, b, n=n)
+        if last:
+            terms.fold(3 * d, a, gk, n=n)
+            terms.fold(3 * d + 1, b, rk, n=n)
+            terms.fold(3 * d + 2, a, fk, n=n)
+
+    def _fold(self, terms, y_hat, y):
+        _no_grad_inputs(y_hat, y)
+        y_hat, y = self._waveforms(y_hat, y)
+        x = torch.cat([y_hat.to(terms.sum.device, torch.float32), y.to(terms.sum.device, torch.float32)], 0)
+        plan = self._plan()
         for d, l, t, n_layers in self.discriminator.layers_of(x):
             half = t.numel() // 2                         # rows [0, B) are y_hat, rows [B, 2B) are y
-            last = l == n_layers - 1
-            if self.feat_match is not None and (not last or self.feat_match.include_final_outputs):
-                terms.fold(fm_off[d] + l, t, LOSS_L1, t.view(-1)[half:], n=half)
-            if last:
-                terms.fold(3 * d, t, gk, n=half)
-                terms.fold(3 * d + 1, t.view(-1)[half:], rk, n=half)
-                terms.fold(3 * d + 2, t, fk, n=half)
+            self._fold_layer(terms, plan, d, l, l == n_layers - 1, t, t.view(-1)[half:], n=half)
             del t
 
     def _combine(self, means):
@@ -830,11 +856,7 @@ class AdversarialEval:
 
     def _forward_grad(self, dev, y_hat, y):
         _no_grad_inputs(y)
-        y_hat, y = _settled(y_hat), _settled(y)
-        if tuple(y_hat.shape) != tuple(y.shape):
-            raise ValueError(f"y_hat {tuple(y_hat.shape)} and y {tuple(y.shape)} must have the same shape")
-        if y.dim() == 2:
-            y_hat, y = y_hat[:, None], y[:, None]
+        y_hat, y = self._waveforms(y_hat, y)
         with torch.no_grad():
             real = [_flat(t) for _, _, t, _ in self.discriminator.layers_of(y)]
         hats, where = [], []
@@ -843,25 +865,18 @@ class AdversarialEval:
             where.append((d, l, l == n_layers - 1))
         flat = [_flat(t, True) for t in hats]
         n_d, fm = self._layout()
-        fm_off = [3 * n_d + sum(fm[:d]) for d in range(n_d)]
-        gk, _ = self.gen_adv.kind()
-        (rk, _), (fk, _) = self.dis_adv.kinds()
-        used = [self.feat_match is not None and (not last or self.feat_match.include_final_outputs) for _, _, last in where]
-        plain = {}
+        plan, plain = self._plan(), {}
 
         def value():
             terms = self._new_terms(dev)
-            for (d, l, last), a, b, fm_term in zip(where, flat, real, used):
-                if fm_term:
-                    terms.fold(fm_off[d] + l, a, LOSS_L1, b)
-                if last:
-                    terms.fold(3 * d, a, gk)
-                    terms.fold(3 * d + 1, b, rk)
-                    terms.fold(3 * d + 2, a, fk)
+            for (d, l, last), a, b in zip(where, flat, real):
+                self._fold_layer(terms, plan, d, l, last, a, b)
             plain.update({k: v.to(torch.float32) for k, v in self._combine(terms.means()).items()})
             return tuple(plain[k] for k in ("adversarial_loss", "feature_matching_loss") if k in plain)
 
+        used = [self._fm_used(last) for _, _, last in where]
         fm_coefs = iter(self.feat_match.coefs([a.numel() for a, u in zip(flat, used) if u], fm)) if self.feat_match else None
+        gk = plan[1]
         terms = []
         for i, ((d, l, last), a, b, fm_term) in enumerate(zip(where, flat, real, used)):
             if fm_term:

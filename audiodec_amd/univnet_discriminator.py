@@ -133,55 +133,33 @@ def _check_grad_layers(layers):
             raise NotImplementedError(f"{L.key}: C_out * kh * kw = {kg} is beyond the HIP 2-D conv backward's {GRAD_GEMM_MAX_K}")
 
 
-class _Conv2d:
-    """One spectral layer's device weights."""
+class _Conv2d(D._ConvBase):
+    """One spectral layer on (N, C, H, W)."""
+    _native = ("adk_conv2d", "adk_conv2d_grad")
+    _impl = staticmethod(conv_impl)
+    _pack_grad = staticmethod(pack_grad_weights2d)
 
-    def __init__(self, layer, w, b, dev):
-        self.layer, self.impl = layer, conv_impl(layer)
-        self._w_grad = None                                                    # the backward's GEMM packing, made on first use
+    def _pack(self, w):
+        layer = self.layer
         kg = layer.cin * layer.kernel[0] * layer.kernel[1]
-        if self.impl == IMPL_GEMM:
-            if kg > GEMM_MAX_K:
-                raise NotImplementedError(f"{layer.key}: C_in * kh * kw = {kg} is beyond the HIP 2-D conv's {GEMM_MAX_K}")
-            w = w.reshape(layer.cout, kg).t()                                   # [cin * kh * kw][cout]
-        self.w = w.contiguous().to(dev)
-        self.b = b.float().contiguous().to(dev) if b is not None else None
+        if kg > GEMM_MAX_K:
+            raise NotImplementedError(f"{layer.key}: C_in * kh * kw = {kg} is beyond the HIP 2-D conv's {GEMM_MAX_K}")
+        return w.reshape(layer.cout, kg).t()                                    # [cin * kh * kw][cout]
 
-    def grad_weights(self):
-        """The weights adk_conv2d_grad reads: the reference's layout for the direct kernel, pack_grad_weights2d for the GEMM
-        (re-packed once, on the device, from the forward packing)."""
-        if self.impl != IMPL_GEMM:
-            return self.w
-        if self._w_grad is None:
-            L = self.layer
-            self._w_grad = pack_grad_weights2d(self.w.t().reshape(L.weight_shape), L)
-        return self._w_grad
+    def _unpack(self, w):
+        return w.t().reshape(self.layer.weight_shape)
 
-    def grad(self, dy, y, x_shape):
-        """dy, y (N, C_out, H', W') contiguous float32 -> dx of x_shape (N, C_in, H, W)."""
+    def _out_shape(self, x_shape):
         L = self.layer
-        n, cin, h, w = x_shape
-        dx = torch.empty(n, cin, h, w, dtype=torch.float32, device=dy.device)
-        act = ACT_LEAKY if L.act_slope is not None else ACT_NONE
-        native.check(native.lib().adk_conv2d_grad(_ptr(dy), _ptr(y) if act else None, _ptr(self.grad_weights()), _ptr(dx), n, cin, h,
-                                                  w, L.cout, L.kernel[0], L.kernel[1], L.stride[0], L.stride[1], L.pad[0], L.pad[1],
-                                                  act, float(L.act_slope or 0.0), self.impl, native.current_stream(dy.device)),
-                     "adk_conv2d_grad")
-        return dx
-
-    def __call__(self, x):
-        """x (N, C_in, H, W) contiguous float32 -> (N, C_out, H', W')."""
-        L = self.layer
-        n, cin, h, w = x.shape
+        n, _, h, w = x_shape
         ho, wo = conv2d_out_shape(h, w, L)
         if ho < 1 or wo < 1:
             raise ValueError(f"{L.key}: input plane {h} x {w} is smaller than the kernel {L.kernel} with padding {L.pad}")
-        y = torch.empty(n, L.cout, ho, wo, dtype=torch.float32, device=x.device)
-        act = ACT_LEAKY if L.act_slope is not None else ACT_NONE
-        native.check(native.lib().adk_conv2d(_ptr(x), _ptr(self.w), _ptr(self.b), _ptr(y), n, cin, h, w, L.cout, L.kernel[0],
-                                             L.kernel[1], L.stride[0], L.stride[1], L.pad[0], L.pad[1], act,
-                                             float(L.act_slope or 0.0), self.impl, native.current_stream(x.device)), "adk_conv2d")
-        return y
+        return n, L.cout, ho, wo
+
+    def _geometry(self):
+        L = self.layer
+        return (L.cout, *L.kernel, *L.stride, *L.pad)
 
 
 def spectrogram(x, window, fft_size, hop_size, win_length):
