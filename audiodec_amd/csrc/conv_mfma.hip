@@ -44,10 +44,9 @@
 // v_mfma_f32_32x32x16_f16 per accumulator pair (hi*hi -> main, hi*lo + lo*hi -> cross) instead of
 // 32 v_mfma_f32_32x32x2_f32; main + cross/2048 is formed when a segment ends.  See conv_rl16.hip for the
 // error analysis.
-#include "adk_common.h"
+#include "conv_split16.h"      // the split-f16 operand format (SPLIT variants), act_in, buf_load4, the vector typedefs
 #include <cstdlib>
 #include <cstring>
-#include <type_traits>
 #include <atomic>
 #include <mutex>
 
@@ -76,11 +75,6 @@ __device__ unsigned long long g_sk_trace[64 * 8];
 #define SK_STAMP(slot) do { } while (0)
 #endif
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8s __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4s __attribute__((ext_vector_type(4)));
-constexpr float kSkLoScale = 2048.f, kSkLoInv = 1.f / 2048.f;
-
 constexpr int KC = 64;    // K chunk: two 32-channel half-chunks (each one tap x 32 channels)
 constexpr int kGvCounters = 4096;      // arrival counters of conv_gv16 at the end of the workspace: one per (group, 32-row m-tile) of a launch
 
@@ -106,13 +100,6 @@ struct SkArgs {
 };
 
 constexpr int kActPre = 100;   // ACT template value of the stream-K kernel: the staged pieces come from a shadow ring, already activated and split
-
-template <int ACT>
-__device__ __forceinline__ float act_in_apply(float x, float slope) {
-    if (ACT == ADK_ACT_ELU) return x > 0.f ? x : expm1_neg(x);
-    if (ACT == ADK_ACT_LEAKY) return x > 0.f ? x : x * slope;
-    return x;
-}
 
 // first work unit of range r (r = G: one past the last) -- shared by the kernels and adk_streamk_range_start
 __host__ __device__ __forceinline__ long long sk_range_start(int r, int G, int split, int tpw, int tiles, int nchunks, int owner_chunks, long long total) {
@@ -159,7 +146,7 @@ __device__ __forceinline__ void sk_epilogue(const ConvArgs& a, const f32x16 (&ac
             if (ml >= a.cout_g) continue;
             const int mg = g * a.cout_g + ml;
             float4 v = make_float4(acc[j][4 * qd], acc[j][4 * qd + 1], acc[j][4 * qd + 2], acc[j][4 * qd + 3]);
-            if (CHECK) bad |= !(fabsf(v.x) <= 3.0e38f) | !(fabsf(v.y) <= 3.0e38f) | !(fabsf(v.z) <= 3.0e38f) | !(fabsf(v.w) <= 3.0e38f);
+            if (CHECK) bad |= not_finite4(v);
             if (a.bias) {
                 const float4 bb = *reinterpret_cast<const float4*>(a.bias + mg);
                 v.x += bb.x; v.y += bb.y; v.z += bb.z; v.w += bb.w;
@@ -183,17 +170,13 @@ __device__ __forceinline__ void sk_epilogue(const ConvArgs& a, const f32x16 (&ac
                 // DMA-fed kernel below; this lane's 4 channels are half of such a group: two 8-byte stores
                 const float x[4] = {act_apply(v.x, a.sh_act, a.sh_slope), act_apply(v.y, a.sh_act, a.sh_slope),
                                     act_apply(v.z, a.sh_act, a.sh_slope), act_apply(v.w, a.sh_act, a.sh_slope)};
-                f16x4s hi, lo;
+                f16x4 hi, lo;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const _Float16 h = (_Float16)x[e];
-                    hi[e] = h;
-                    lo[e] = (_Float16)((x[e] - (float)h) * kSkLoScale);
-                }
+                for (int e = 0; e < 4; ++e) split_to(x[e], hi, lo, e);
                 unsigned char* srow = reinterpret_cast<unsigned char*>(a.out_sh + ((size_t)b * a.out_rows + orow) * a.out_ch + a.out_choff);
                 unsigned char* sp = srow + (size_t)(ocol >> 3) * 32 + (ocol & 4) * 2;           // group ocol / 8, first or second half of its hi block
-                *reinterpret_cast<f16x4s*>(sp) = hi;
-                *reinterpret_cast<f16x4s*>(sp + 16) = lo;
+                *reinterpret_cast<f16x4*>(sp) = hi;
+                *reinterpret_cast<f16x4*>(sp + 16) = lo;
             }
         }
     }
@@ -207,13 +190,6 @@ __device__ __forceinline__ void sk_tile_coords(int tile, const SkArgs& sk, int& 
     const int rest = tile / sk.m_tiles;
     nt = rest % sk.n_tiles;
     g = rest / sk.n_tiles;
-}
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float4 buf_load4(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff) {
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 0);
-    return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
 }
 
 // n / d for 0 <= n < 2^24 via the f32 reciprocal (exact after one correction step)
@@ -254,8 +230,8 @@ __device__ __forceinline__ void sk_epilogue_lds(const ConvArgs& a, const f32x16 
         if (n >= a.n_total || ml >= a.cout_g) continue;
         float4 t0 = *reinterpret_cast<const float4*>(T + (size_t)col * TSF + 8 * cg);
         float4 t1 = *reinterpret_cast<const float4*>(T + (size_t)col * TSF + 8 * cg + 4);
-        if (CHECK) bad |= !(fabsf(t0.x) <= 3.0e38f) | !(fabsf(t0.y) <= 3.0e38f) | !(fabsf(t0.z) <= 3.0e38f) | !(fabsf(t0.w) <= 3.0e38f) |
-                          !(fabsf(t1.x) <= 3.0e38f) | !(fabsf(t1.y) <= 3.0e38f) | !(fabsf(t1.z) <= 3.0e38f) | !(fabsf(t1.w) <= 3.0e38f);
+        if (CHECK) bad |= not_finite(t0.x) | not_finite(t0.y) | not_finite(t0.z) | not_finite(t0.w) |
+                          not_finite(t1.x) | not_finite(t1.y) | not_finite(t1.z) | not_finite(t1.w);
         const int b = fast_div(n, a.t_out, inv_t_out), t = n - b * a.t_out;
         const int mg = g * a.cout_g + ml;
         if (a.bias) {
@@ -283,17 +259,12 @@ __device__ __forceinline__ void sk_epilogue_lds(const ConvArgs& a, const f32x16 
         *reinterpret_cast<float4*>(a.out + oidx) = make_float4(x[0], x[1], x[2], x[3]);
         *reinterpret_cast<float4*>(a.out + oidx + 4) = make_float4(x[4], x[5], x[6], x[7]);
         if (CHECK && a.out_sh) {
-            f16x8s hi, lo;
+            f16x8 hi, lo;
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float y = act_apply(x[e], a.sh_act, a.sh_slope);
-                const _Float16 h = (_Float16)y;
-                hi[e] = h;
-                lo[e] = (_Float16)((y - (float)h) * kSkLoScale);
-            }
+            for (int e = 0; e < 8; ++e) split_to(act_apply(x[e], a.sh_act, a.sh_slope), hi, lo, e);
             unsigned char* sp = reinterpret_cast<unsigned char*>(a.out_sh + ((size_t)b * a.out_rows + orow) * a.out_ch + a.out_choff) + (size_t)(ocol >> 3) * 32;
-            *reinterpret_cast<f16x8s*>(sp) = hi;
-            *reinterpret_cast<f16x8s*>(sp + 16) = lo;
+            *reinterpret_cast<f16x8*>(sp) = hi;
+            *reinterpret_cast<f16x8*>(sp + 16) = lo;
         }
     }
     if (CHECK && bad) atomicOr(err, 8);
@@ -451,22 +422,22 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN == 4) ? 2 : 1) void conv
         } else {
             float4 v = rb[rr];
             if (!(SPLIT && (ADK_SK16_DBG & 2))) {
-                v.x = act_in_apply<ACT>(v.x, a.slope); v.y = act_in_apply<ACT>(v.y, a.slope);
-                v.z = act_in_apply<ACT>(v.z, a.slope); v.w = act_in_apply<ACT>(v.w, a.slope);
+                v.x = act_in<ACT>(v.x, a.slope); v.y = act_in<ACT>(v.y, a.slope);
+                v.z = act_in<ACT>(v.z, a.slope); v.w = act_in<ACT>(v.w, a.slope);
             }
             if constexpr (SPLIT) {
                 // column row = [KCC halfs hi][KCC halfs lo][16 B pad]; this thread's 4 floats -> 2 x 8 bytes
-                f16x4s hi, lo;
+                f16x4 hi, lo;
                 const float x[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const _Float16 h = (_Float16)x[e];
                     hi[e] = h;
-                    lo[e] = (ADK_SK16_DBG & 1) ? (_Float16)0.f : (_Float16)((x[e] - (float)h) * kSkLoScale);
+                    lo[e] = (ADK_SK16_DBG & 1) ? (_Float16)0.f : lo_part(x[e], h);
                 }
                 unsigned char* d = reinterpret_cast<unsigned char*>(Bb + (srow + CPR * rr) * LDK) + 8 * quad;
-                *reinterpret_cast<f16x4s*>(d) = hi;
-                *reinterpret_cast<f16x4s*>(d + 2 * KCC) = lo;
+                *reinterpret_cast<f16x4*>(d) = hi;
+                *reinterpret_cast<f16x4*>(d + 2 * KCC) = lo;
             } else {
                 *reinterpret_cast<float4*>(Bb + (srow + CPR * rr) * LDK + 4 * quad) = v;
             }
@@ -575,13 +546,13 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN == 4) ? 2 : 1) void conv
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int st = 0; st < 4; ++st) {
-                union { float4 f; f16x8s h; } ah, al;
+                union { float4 f; f16x8 h; } ah, al;
                 ah.f = a_cur[2 * st]; al.f = a_cur[2 * st + 1];
-                f16x8s bh[NJ], bl[NJ];
+                f16x8 bh[NJ], bl[NJ];
 #pragma unroll
                 for (int j = 0; j < NJ; ++j) {
-                    bh[j] = *reinterpret_cast<const f16x8s*>(Bh + j * 32 * LDK * 4 + 32 * st);
-                    bl[j] = *reinterpret_cast<const f16x8s*>(Bh + j * 32 * LDK * 4 + 32 * st + 2 * KCC);
+                    bh[j] = *reinterpret_cast<const f16x8*>(Bh + j * 32 * LDK * 4 + 32 * st);
+                    bl[j] = *reinterpret_cast<const f16x8*>(Bh + j * 32 * LDK * 4 + 32 * st + 2 * KCC);
                 }
 #pragma unroll
                 for (int j = 0; j < NJ; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah.h, bh[j], acc[j], 0, 0, 0);
@@ -607,13 +578,13 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN == 4) ? 2 : 1) void conv
             const unsigned char* Bh = reinterpret_cast<const unsigned char*>(Bb);     // + 4*lh floats = 16*lh bytes: this lane's 8 halfs
 #pragma unroll
             for (int st = 0; st < 4 * KD; ++st) {
-                union { float4 f; f16x8s h; } ah, al;
+                union { float4 f; f16x8 h; } ah, al;
                 ah.f = a_cur[2 * st]; al.f = a_cur[2 * st + 1];
-                f16x8s bh[NJ], bl[NJ];
+                f16x8 bh[NJ], bl[NJ];
 #pragma unroll
                 for (int j = 0; j < NJ; ++j) {
-                    bh[j] = *reinterpret_cast<const f16x8s*>(Bh + j * 32 * LDK * 4 + 32 * st);
-                    bl[j] = *reinterpret_cast<const f16x8s*>(Bh + j * 32 * LDK * 4 + 32 * st + 2 * KCC);
+                    bh[j] = *reinterpret_cast<const f16x8*>(Bh + j * 32 * LDK * 4 + 32 * st);
+                    bl[j] = *reinterpret_cast<const f16x8*>(Bh + j * 32 * LDK * 4 + 32 * st + 2 * KCC);
                 }
 #pragma unroll
                 for (int j = 0; j < NJ; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah.h, bh[j], acc[j], 0, 0, 0);
@@ -660,7 +631,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN == 4) ? 2 : 1) void conv
 #pragma unroll
                 for (int j = 0; j < NJ; ++j)
 #pragma unroll
-                    for (int e = 0; e < 16; ++e) { acc[j][e] = fmaf(accx[j][e], kSkLoInv, acc[j][e]); accx[j][e] = 0.f; }
+                    for (int e = 0; e < 16; ++e) { acc[j][e] = join(acc[j][e], accx[j][e]); accx[j][e] = 0.f; }
             }
             const bool seg_first = (seg_start_kc == 0);            // segment holds the tile's first chunk
             const bool seg_last = (kc == sk.nchunks - 1);          // ... and its last chunk
@@ -680,7 +651,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN == 4) ? 2 : 1) void conv
                         v.z = __float_as_uint(acc[j][4 * e4 + 2]); v.w = __float_as_uint(acc[j][4 * e4 + 3]);
                         __builtin_amdgcn_raw_buffer_store_b128(v, rsrc_ws, wbase + (unsigned)((j * 4 + e4) * (NT * 16)), 0, 16 /* sc1 */);
                     }
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every storing wave drains
+                wait_vm<0>();                                      // every storing wave drains
                 __syncthreads();
                 if (tid == 0) __hip_atomic_store(sk.flags + r, sk.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             } else {
@@ -869,29 +840,22 @@ __global__ __launch_bounds__(64) void conv_gv16_kernel(ConvArgs a, GvArgs gv) {
     for (int e = 0; e < 16; ++e) { acc[0][e] = 0.f; accx[e] = 0.f; }
 #pragma unroll
     for (int i = 0; i < MAXS; ++i) {
-        union { u32x4 u; f16x8s h; } Ah, Al;
-        Ah.u = ah[i]; Al.u = al[i];
-        f16x8s bh, bl;
+        const f16x8 Ah = as_f16x8(ah[i]), Al = as_f16x8(al[i]);
+        f16x8 bh, bl;
         if constexpr (ACT == kActPre) {
-            union { float4 f; f16x8s h; } c0, c1;
+            union { float4 f; f16x8 h; } c0, c1;
             c0.f = x0[i]; c1.f = x1[i];
             bh = c0.h; bl = c1.h;
         } else {
             const float x[8] = {x0[i].x, x0[i].y, x0[i].z, x0[i].w, x1[i].x, x1[i].y, x1[i].z, x1[i].w};
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float y = act_in_apply<ACT>(x[e], a.slope);
-                const _Float16 h = (_Float16)y;
-                bh[e] = h;
-                bl[e] = (_Float16)((y - (float)h) * kSkLoScale);
-            }
+            act_split<ACT>(x, a.slope, bh, bl);
         }
-        acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah.h, bh, acc[0], 0, 0, 0);
-        accx = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah.h, bl, accx, 0, 0, 0);
-        accx = __builtin_amdgcn_mfma_f32_32x32x16_f16(Al.h, bh, accx, 0, 0, 0);
+        acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, bh, acc[0], 0, 0, 0);
+        accx = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, bl, accx, 0, 0, 0);
+        accx = __builtin_amdgcn_mfma_f32_32x32x16_f16(Al, bh, accx, 0, 0, 0);
     }
 #pragma unroll
-    for (int e = 0; e < 16; ++e) acc[0][e] = fmaf(accx[e], kSkLoInv, acc[0][e]);
+    for (int e = 0; e < 16; ++e) acc[0][e] = join(acc[0][e], accx[e]);
 
     if (gv.S > 1) {
         // publish this slice's partial sums (write-through), count in; the last slice to arrive adds all of them in slice order
@@ -904,7 +868,7 @@ __global__ __launch_bounds__(64) void conv_gv16_kernel(ConvArgs a, GvArgs gv) {
             v.z = __float_as_uint(acc[0][4 * q + 2]); v.w = __float_as_uint(acc[0][4 * q + 3]);
             __builtin_amdgcn_raw_buffer_store_b128(v, rsrc_ws, pbase + (unsigned)q * 1024u, 0, 16 /* sc1 */);
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vm<0>();
         unsigned old = 0;
         if (lane == 0) old = __hip_atomic_fetch_add(gv.counters + otile, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         old = __builtin_amdgcn_readfirstlane(old);
@@ -954,17 +918,13 @@ __global__ void pack_weights_kernel(const float* __restrict__ w, float* __restri
 }
 
 bool conv_mfma_supported(const ConvArgs& a) {
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     if (!a.wfrag) return false;
     // 32-bit buffer addressing: input arena view < 2 GiB, packed weights < 4 GiB, N < 2^24
     if ((unsigned long long)a.batch * a.in_rows * a.in_ch * 4ull >= 0x80000000ull) return false;
     if ((unsigned long long)a.groups * ((a.cout_g + 31) / 32) * ((a.ktot + 63) / 64 * 8) * 1024ull >= 0xfff00000ull) return false;
     if (a.n_total >= (1 << 24)) return false;
     if (a.cin_g % 32 != 0 || a.cout_g % 4 != 0 || a.cout_real % 4 != 0) return false;
-    if (a.in_ch % 4 || a.in_choff % 4 || a.in_gstride % 4 || a.out_ch % 4 || a.out_choff % 4) return false;
-    if (!al16(a.in) || !al16(a.out) || !al16(a.wfrag) || (a.bias && !al16(a.bias))) return false;
-    if (a.res && (a.res_ch % 4 || a.res_choff % 4 || a.res_gstride % 4 || !al16(a.res))) return false;
-    return true;
+    return conv_io_aligned(a);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1095,16 +1055,11 @@ int launch_cfg(const ConvArgs& a, hipStream_t s, Workspace& ws) {
             return ADK_OK;
         }
     }
-    if (a.act_in == ADK_ACT_ELU)
-        hipLaunchKernelGGL((conv_sk_kernel<WGM, WGN, NJ, ADK_ACT_ELU, SPLIT, KD>), dim3(grid), dim3(NT), lds, s, a, sk);
-    else if (a.act_in == ADK_ACT_LEAKY)
-        hipLaunchKernelGGL((conv_sk_kernel<WGM, WGN, NJ, ADK_ACT_LEAKY, SPLIT, KD>), dim3(grid), dim3(NT), lds, s, a, sk);
-    else if (a.act_in == ADK_ACT_NONE)
-        hipLaunchKernelGGL((conv_sk_kernel<WGM, WGN, NJ, ADK_ACT_NONE, SPLIT, KD>), dim3(grid), dim3(NT), lds, s, a, sk);
-    else
-        return fail(ADK_ERR_ARG, "conv: unsupported input activation for the MFMA kernel");
-    ADK_HIP_CHECK(hipGetLastError());
-    return ADK_OK;
+    return with_act_in(a.act_in, "conv: unsupported input activation for the MFMA kernel", [&](auto act) -> int {
+        hipLaunchKernelGGL((conv_sk_kernel<WGM, WGN, NJ, decltype(act)::value, SPLIT, KD>), dim3(grid), dim3(NT), lds, s, a, sk);
+        ADK_HIP_CHECK(hipGetLastError());
+        return ADK_OK;
+    });
 }
 }  // namespace
 
@@ -1243,16 +1198,15 @@ int launch_conv_gv16(const ConvArgs& a, hipStream_t s, Workspace& ws) {
     ConvArgs b = a;
     int act = a.act_in;
     if (a.in_sh) { b.in = a.in_sh; act = kActPre; }
-#define ADK_GV_LAUNCH(ACT_) do { if (small) hipLaunchKernelGGL((conv_gv16_kernel<ACT_, 12>), dim3(grid), dim3(64), 0, s, b, gv); \
-                                 else hipLaunchKernelGGL((conv_gv16_kernel<ACT_, 24>), dim3(grid), dim3(64), 0, s, b, gv); } while (0)
-    if (act == kActPre) ADK_GV_LAUNCH(kActPre);
-    else if (act == ADK_ACT_ELU) ADK_GV_LAUNCH(ADK_ACT_ELU);
-    else if (act == ADK_ACT_LEAKY) ADK_GV_LAUNCH(ADK_ACT_LEAKY);
-    else if (act == ADK_ACT_NONE) ADK_GV_LAUNCH(ADK_ACT_NONE);
-    else return fail(ADK_ERR_ARG, "conv: unsupported input activation for the MFMA kernel");
-#undef ADK_GV_LAUNCH
-    ADK_HIP_CHECK(hipGetLastError());
-    return ADK_OK;
+    auto go = [&](auto act_c) -> int {
+        constexpr int ACT = decltype(act_c)::value;
+        if (small) hipLaunchKernelGGL((conv_gv16_kernel<ACT, 12>), dim3(grid), dim3(64), 0, s, b, gv);
+        else hipLaunchKernelGGL((conv_gv16_kernel<ACT, 24>), dim3(grid), dim3(64), 0, s, b, gv);
+        ADK_HIP_CHECK(hipGetLastError());
+        return ADK_OK;
+    };
+    if (act == kActPre) return go(std::integral_constant<int, kActPre>());
+    return with_act_in(act, "conv: unsupported input activation for the MFMA kernel", go);
 }
 
 int launch_conv_sk16(const ConvArgs& a, hipStream_t s, Workspace& ws) {

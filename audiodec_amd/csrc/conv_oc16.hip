@@ -16,17 +16,13 @@
 //   * the output conv is exact f32 on the vector ALU, one lane per step, taps outer / channels inner -- the order of conv_cout1_kernel, so
 //     that part of the result is bit-identical to the two-launch form -- then + bias, tanh, one coalesced store.
 // GEMM 1 sums the same products in the same 16-k chunks as conv_sk16 does for this conv (K = 96: no stream-K cut).
-#include "adk_common.h"
-#include <type_traits>
+// Operand format, act_in, join4, ADK_LDS_DMA16, wait_vm: conv_split16.h.
+#include "conv_split16.h"
 #include <cstdlib>
 
 namespace adk {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8u __attribute__((ext_vector_type(8)));
-
-constexpr float kOcLoScale = 2048.f, kOcLoInv = 1.f / 2048.f;
 constexpr int OC_CIN = 96, OC_CM = 32, OC_TAPS = 7, OC_HALO = OC_TAPS - 1;
 constexpr int OC_COLS = 128;                     // GEMM columns per workgroup (4 waves x 32)
 constexpr int OC_SLMAX = OC_COLS - OC_HALO;      // new steps per workgroup at most
@@ -39,21 +35,6 @@ constexpr int OC_STAGE = 2048;                   // [6 x 128 B history of c][128
 constexpr int OC_LDS = OC_W1B + 4 * OC_RING + OC_STAGE;
 
 struct OcArgs { int n_slices, sl; int* err; };
-
-#define OC_DMA16(gptr, m0val) do { unsigned m0_keep_; asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" \
-                                                            : "=&s"(m0_keep_) : "v"(gptr), "s"(m0val) : "memory"); } while (0)      /* M0 is the compiler's: put back */
-template <int N> __device__ __forceinline__ void oc_wait_vm() {
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else static_assert(N == 0, "add the count");
-}
-
-template <int ACT>
-__device__ __forceinline__ float oc_act(float x, float slope) {
-    if (ACT == ADK_ACT_ELU) return x > 0.f ? x : expm1_neg(x);
-    if (ACT == ADK_ACT_LEAKY) return x > 0.f ? x : x * slope;
-    return x;
-}
 
 template <int ACT>
 __global__ __launch_bounds__(256, 3) void conv_oc16_kernel(ConvArgs a1, ConvArgs a2, OcArgs u) {
@@ -72,7 +53,6 @@ __global__ __launch_bounds__(256, 3) void conv_oc16_kernel(ConvArgs a1, ConvArgs
     unsigned char* ring = lds + OC_W1B + wave * OC_RING;
     unsigned char* ring_all = lds + OC_W1B;
     unsigned char* stage = lds + OC_W1B + 4 * OC_RING;
-    typedef unsigned char __attribute__((address_space(3)))* lds_u8_t;
     const unsigned lds0 = (unsigned)(size_t)(lds_u8_t)lds;
     const unsigned lane16 = (unsigned)lane * 16u;
 
@@ -86,19 +66,19 @@ __global__ __launch_bounds__(256, 3) void conv_oc16_kernel(ConvArgs a1, ConvArgs
             if (row >= a2.in_rows) row -= a2.in_rows;
             src = reinterpret_cast<const unsigned char*>(a2.in + ((size_t)b * a2.in_rows + row) * a2.in_ch + a2.in_choff) + 16 * (lane & 7);
         } else if (lane < 8 * OC_HALO + 8) { if (a1.bias) src = reinterpret_cast<const unsigned char*>(a1.bias) + 16 * (lane - 8 * OC_HALO); }
-        OC_DMA16(src, lds0 + (unsigned)(stage - lds));
+        ADK_LDS_DMA16(src, lds0 + (unsigned)(stage - lds));
         src = lane < OC_TAPS * OC_CM / 4 ? reinterpret_cast<const unsigned char*>(a2.w) + lane16 : dummy;
-        OC_DMA16(src, lds0 + (unsigned)(stage - lds) + 1024u);
+        ADK_LDS_DMA16(src, lds0 + (unsigned)(stage - lds) + 1024u);
     }
     {
         const unsigned char* g1 = reinterpret_cast<const unsigned char*>(a1.wfrag) + (size_t)tid * 16;
         const unsigned l1 = lds0 + (unsigned)wave * 1024u;
 #pragma unroll
-        for (int i = 0; i < OC_W1B / 4096; ++i) OC_DMA16(g1 + 4096 * i, l1 + 4096u * i);
+        for (int i = 0; i < OC_W1B / 4096; ++i) ADK_LDS_DMA16(g1 + 4096 * i, l1 + 4096u * i);
     }
     float chk = 0.f;                                        // stays 0 while every c is finite
     if (!act_w) {
-        oc_wait_vm<0>();
+        wait_vm<0>();
         __syncthreads();
     } else {
         // this lane's source of piece (instruction j, column block cb): row r = 8 j + lane / 8 of the tile, 16-byte piece (lane & 7) ^ ((r >> 1) & 7)
@@ -116,7 +96,7 @@ __global__ __launch_bounds__(256, 3) void conv_oc16_kernel(ConvArgs a1, ConvArgs
         auto issue_block = [&](int cb) __attribute__((always_inline)) {
             const unsigned dst = ring0 + (unsigned)(cb & 1) * OC_SLOT;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) OC_DMA16(xsrc[j] + 128 * cb, dst + 1024u * j);
+            for (int j = 0; j < 4; ++j) ADK_LDS_DMA16(xsrc[j] + 128 * cb, dst + 1024u * j);
         };
         issue_block(0); issue_block(1);
 
@@ -128,9 +108,9 @@ __global__ __launch_bounds__(256, 3) void conv_oc16_kernel(ConvArgs a1, ConvArgs
 #pragma unroll
         for (int cb = 0; cb < OC_NCB; ++cb) {
             // in flight at most (11 issued up front, + 4 for block 2):
-            if (cb == 0) { oc_wait_vm<4>(); __syncthreads(); }          // {stage, W1, block 0} landed here -- and, behind the barrier, everybody's W1 and wave 0's stage
-            else if (cb == 1) oc_wait_vm<4>();                          // block 1; block 2 may stay in flight
-            else oc_wait_vm<0>();
+            if (cb == 0) { wait_vm<4>(); __syncthreads(); }          // {stage, W1, block 0} landed here -- and, behind the barrier, everybody's W1 and wave 0's stage
+            else if (cb == 1) wait_vm<4>();                          // block 1; block 2 may stay in flight
+            else wait_vm<0>();
             const unsigned char* xs = ring + (cb & 1) * OC_SLOT + l31 * 128;
             float4 xr[2][2];
 #pragma unroll
@@ -144,15 +124,10 @@ __global__ __launch_bounds__(256, 3) void conv_oc16_kernel(ConvArgs a1, ConvArgs
 #pragma unroll
             for (int sc = 0; sc < 2; ++sc) {
                 const unsigned char* wp = w1l + (size_t)(2 * cb + sc) * 2048 + lane * 16;
-                const f16x8u Ah = *reinterpret_cast<const f16x8u*>(wp);
-                const f16x8u Al = *reinterpret_cast<const f16x8u*>(wp + 1024);
-                const float x[8] = {xr[sc][0].x, xr[sc][0].y, xr[sc][0].z, xr[sc][0].w, xr[sc][1].x, xr[sc][1].y, xr[sc][1].z, xr[sc][1].w};
-                f16x8u bh, bl;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const _Float16 h = (_Float16)x[e];
-                    bh[e] = h; bl[e] = (_Float16)((x[e] - (float)h) * kOcLoScale);
-                }
+                const f16x8 Ah = *reinterpret_cast<const f16x8*>(wp);
+                const f16x8 Al = *reinterpret_cast<const f16x8*>(wp + 1024);
+                f16x8 bh, bl;
+                split8(xr[sc][0], xr[sc][1], bh, bl);
                 am = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, bh, am, 0, 0, 0);
                 ac = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, bl, ac, 0, 0, 0);
                 ac = __builtin_amdgcn_mfma_f32_32x32x16_f16(Al, bh, ac, 0, 0, 0);
@@ -174,8 +149,7 @@ __global__ __launch_bounds__(256, 3) void conv_oc16_kernel(ConvArgs a1, ConvArgs
 #pragma unroll
         for (int qd = 0; qd < 4; ++qd) {
             const int ml = 8 * qd + 4 * lh;
-            float4 v = make_float4(fmaf(ac[4 * qd], kOcLoInv, am[4 * qd]), fmaf(ac[4 * qd + 1], kOcLoInv, am[4 * qd + 1]),
-                                   fmaf(ac[4 * qd + 2], kOcLoInv, am[4 * qd + 2]), fmaf(ac[4 * qd + 3], kOcLoInv, am[4 * qd + 3]));
+            float4 v = join4(am, ac, qd);
             chk = fmaf(v.x, 0.f, chk); chk = fmaf(v.y, 0.f, chk); chk = fmaf(v.z, 0.f, chk); chk = fmaf(v.w, 0.f, chk);
             if (a1.bias) {
                 const float4 bb = *reinterpret_cast<const float4*>(b1l + ml);
@@ -183,7 +157,7 @@ __global__ __launch_bounds__(256, 3) void conv_oc16_kernel(ConvArgs a1, ConvArgs
             }
             if (from_hist) v = *reinterpret_cast<const float4*>(hist + ml);
             if (to_ring) *reinterpret_cast<float4*>(cdst + ml) = v;
-            v.x = oc_act<ACT>(v.x, a2.slope); v.y = oc_act<ACT>(v.y, a2.slope); v.z = oc_act<ACT>(v.z, a2.slope); v.w = oc_act<ACT>(v.w, a2.slope);
+            v.x = act_in<ACT>(v.x, a2.slope); v.y = act_in<ACT>(v.y, a2.slope); v.z = act_in<ACT>(v.z, a2.slope); v.w = act_in<ACT>(v.w, a2.slope);
             *reinterpret_cast<float4*>(crow + 4 * ml) = v;
         }
     }
@@ -212,8 +186,6 @@ __global__ __launch_bounds__(256, 3) void conv_oc16_kernel(ConvArgs a1, ConvArgs
     if (!(chk == 0.f)) atomicOr(u.err, 8);
 }
 
-bool oc_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 // a1: the 1x1 conv 96 -> 32, a2: the K7 conv 32 -> 1 that reads exactly what a1 writes
@@ -225,9 +197,9 @@ bool conv_oc16_fusable(const ConvArgs& a1, const ConvArgs& a2) {
     if (a1.batch != a2.batch || a1.t_out != a2.t_out || a1.t_out < 1) return false;
     if (a2.in != a1.out || a2.in_rows != a1.out_rows || a2.in_ch != a1.out_ch || a2.in_choff != a1.out_choff || a1.out_rows < a1.t_out + OC_HALO) return false;
     if (a2.in_row0 != (a1.out_cursor + a1.out_rows - OC_HALO) % a1.out_rows) return false;       // six steps of history, right in front of the new rows
-    if ((a1.in_ch % 4) || (a1.in_choff % 4) || (a1.out_ch % 4) || (a1.out_choff % 4) || !oc_aligned16(a1.in) || !oc_aligned16(a1.out) || !oc_aligned16(a1.wfrag) ||
-        !oc_aligned16(a2.w)) return false;
-    if (a1.bias && !oc_aligned16(a1.bias)) return false;
+    if ((a1.in_ch % 4) || (a1.in_choff % 4) || (a1.out_ch % 4) || (a1.out_choff % 4) || !aligned16(a1.in) || !aligned16(a1.out) || !aligned16(a1.wfrag) ||
+        !aligned16(a2.w)) return false;
+    if (a1.bias && !aligned16(a1.bias)) return false;
     return true;
 }
 
@@ -241,15 +213,12 @@ int launch_conv_oc16(const ConvArgs& a1, const ConvArgs& a2, hipStream_t s) {
     u.err = conv_err_word(a1);
     const long long blocks = (long long)a1.batch * u.n_slices;
     if (blocks > 0x7fffffffLL) return ADK_ERR_STATE;
-    auto go = [&](auto act) -> int {
+    return with_act_in(a2.act_in, nullptr, [&](auto act) -> int {
         constexpr int ACT = decltype(act)::value;
         hipLaunchKernelGGL(conv_oc16_kernel<ACT>, dim3((unsigned)blocks), dim3(256), OC_LDS, s, a1, a2, u);
         ADK_HIP_CHECK(hipGetLastError());
         return ADK_OK;
-    };
-    if (a2.act_in == ADK_ACT_ELU) return go(std::integral_constant<int, ADK_ACT_ELU>());
-    if (a2.act_in == ADK_ACT_LEAKY) return go(std::integral_constant<int, ADK_ACT_LEAKY>());
-    return go(std::integral_constant<int, ADK_ACT_NONE>());
+    });
 }
 
 }  // namespace adk

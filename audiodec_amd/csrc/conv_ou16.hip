@@ -19,8 +19,8 @@
 // transposed conv); the 16 x 16 x 32 MFMA groups the f32 additions differently from their 32 x 32 x 16: equal to f32 round-off, not bit for bit.
 // Earlier forms, not compiled: experiments/conv_ou16_round3_register_fed.hip (round 3: operands through registers, 12.5 us at 256 streams in
 // its own clocks), experiments/conv_ou16_round6_four_waves.hip (round 6: this schedule at one wave per SIMD on 32-column tiles, 10.2 us; 8.9 here).
-#include "adk_common.h"
-#include <type_traits>
+// Operand format, act_split4 / split8, join4, ADK_LDS_DMA16, wait_vm: conv_split16.h.
+#include "conv_split16.h"
 #include <cstdlib>
 
 #ifndef ADK_OU16_DBG
@@ -44,25 +44,11 @@ extern "C" int adk_debug_ou_trace(unsigned long long* out, int n) {
 
 namespace {
 
-typedef _Float16 f16x8u __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4u __attribute__((ext_vector_type(4)));
-typedef const void __attribute__((address_space(1)))* gptr_t;
-typedef void __attribute__((address_space(3)))* lptr_t;
-
-constexpr float kOuLoScale = 2048.f, kOuLoInv = 1.f / 2048.f;
 constexpr int OU_CM = 64;                        // channels between the two convs
 constexpr int OU_KS2 = 2 * OU_CM / 16;           // 2 taps x 64 channels = 8 chunks of 16
 constexpr int OU_TMAX = 128;                     // steps of the 1x1 conv per workgroup (8 waves x 16)
 
 struct OuArgs { int ks1p; float inv_cout_real; int* err; unsigned out_bytes; };
-typedef unsigned u32x4o __attribute__((ext_vector_type(4)));
-
-template <int ACT>
-__device__ __forceinline__ float ou_act(float x, float slope) {
-    if (ACT == ADK_ACT_ELU) return x > 0.f ? x : expm1_neg(x);
-    if (ACT == ADK_ACT_LEAKY) return x > 0.f ? x : x * slope;
-    return x;
-}
 
 // Every byte of the launch arrives by LDS-DMA (global_load_lds_dwordx4: lane i's 16 bytes land at M0 + 16 i, lane-linear; the SOURCE address
 // is per lane, which is where the swizzles below come from).  What the timeline of the register-fed kernel of round 3 said
@@ -71,8 +57,7 @@ __device__ __forceinline__ float ou_act(float x, float slope) {
 // 256-byte store behind the s_waitcnt vmcnt(0) that W2's arrival needs.  With DMA the activations come in fully coalesced (whole 128-byte
 // lines), no lane holds staged activations, and no ordinary vector load is left in the kernel -- biases and the history row of c arrive
 // through one more DMA instruction -- so every s_waitcnt vmcnt is written here, counted, and none drains W2 early.
-#define OU_DMA16(gptr, m0val) do { unsigned m0_keep_; asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" \
-                                                            : "=&s"(m0_keep_) : "v"(gptr), "s"(m0val) : "memory"); } while (0)      /* M0 is the compiler's: put back */
+// (ADK_LDS_DMA16 and wait_vm: conv_split16.h)
 constexpr int OU_NCB = 6;                        // column blocks of the 1x1 conv's input: 192 channels / 32
 
 // ================================================================================================
@@ -91,25 +76,9 @@ constexpr int OU_NCB = 6;                        // column blocks of the 1x1 con
 // A 16 x 16 x 32 MFMA sums 32 products per instruction where the 32 x 32 x 16 form sums 16: per output element the same products and the
 // same chunk order, another grouping of the f32 additions -- the result agrees with the four-wave kernel and with conv_sk16 + conv_up16 to
 // f32 round-off (<= 1e-6 on the O(1) outputs), not bit for bit; the same call is bit-reproducible.
-typedef float f32x4m __attribute__((ext_vector_type(4)));
 constexpr int OU8_SLOT = 2048;                   // one column block of a wave's tile: 16 rows x 128 B
 constexpr int OU8_RING = 3 * OU8_SLOT;           // ring of a wave; after GEMM 1 its first 16 * OU8_RSC bytes hold the wave's rows of act(c)
 constexpr int OU8_RSC = 4 * OU_CM + 32;          // row stride of act(c): [64 halfs hi][64 halfs lo][32 B pad] = 288 B = 18 x 16 B: rows 2 slots apart -> conflict-free reads
-
-template <int N> __device__ __forceinline__ void ou8_wait_vm() {
-    static_assert(N >= 0 && N <= 63, "vmcnt is six bits");
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else if constexpr (N == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-    else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if constexpr (N == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-    else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else if constexpr (N == 7) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-    else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if constexpr (N == 9) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-    else if constexpr (N == 10) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-    else static_assert(N == 0, "add the count");
-}
 
 // swizzle of the 16-byte pieces of ring row n (0..15): the two k-groups a ds_read_b128 lane group mixes sit in complementary row sets
 // {0-3, 12-15} / {4-11} and two pieces apart; f maps the second set's pieces onto the other half of the bank row
@@ -136,7 +105,6 @@ __global__ __launch_bounds__(512, 2) void conv_ou16_w8_kernel(ConvArgs a1, ConvA
     unsigned char* halo = w2l + W2B + 8 * OU8_RING;        // [8][OU8_RSC]: act(c) of the step in front of wave w's first one (w = 0: the history row)
     unsigned char* stage0 = halo + 8 * OU8_RSC;            // 1 KiB: {c[-1] | bias 2 | bias 1}, fetched by wave 0
     float* clast = reinterpret_cast<float*>(stage0 + 1024);
-    typedef unsigned char __attribute__((address_space(3)))* lds_u8_t;
     const unsigned lds0 = (unsigned)(size_t)(lds_u8_t)lds;
     const unsigned lane16 = (unsigned)lane * 16u;
     const bool act = __builtin_amdgcn_readfirstlane(wave * 16 < T ? 1 : 0) != 0;     // a wave whose 16 steps all lie past the end only helps with the weights
@@ -154,13 +122,13 @@ __global__ __launch_bounds__(512, 2) void conv_ou16_w8_kernel(ConvArgs a1, ConvA
         if (lane < 16) src = reinterpret_cast<const unsigned char*>(a2.in + ((size_t)b * a2.in_rows + a2.in_row0) * a2.in_ch + a2.in_choff) + lane16;
         else if (lane < 16 + 8 * MT2) { if (a2.bias) src = reinterpret_cast<const unsigned char*>(a2.bias) + (lane - 16) * 16; }
         else if (lane >= 40 && lane < 56) { if (a1.bias) src = reinterpret_cast<const unsigned char*>(a1.bias) + (lane - 40) * 16; }
-        OU_DMA16(src, lds0 + (unsigned)(stage0 - lds));
+        ADK_LDS_DMA16(src, lds0 + (unsigned)(stage0 - lds));
     }
     {
         const unsigned char* g1 = reinterpret_cast<const unsigned char*>(a1.wfrag) + (size_t)tid * 16;
         const unsigned l1 = lds0 + (unsigned)wave * 1024u;
 #pragma unroll
-        for (int i = 0; i < W1B / 8192; ++i) OU_DMA16(g1 + 8192 * i, l1 + 8192u * i);
+        for (int i = 0; i < W1B / 8192; ++i) ADK_LDS_DMA16(g1 + 8192 * i, l1 + 8192u * i);
     }
     const unsigned char* xsrc[2];
 #pragma unroll
@@ -176,14 +144,14 @@ __global__ __launch_bounds__(512, 2) void conv_ou16_w8_kernel(ConvArgs a1, ConvA
     auto issue_block = [&](int cb) __attribute__((always_inline)) {
         const unsigned dst = ring0 + (unsigned)(cb % 3) * OU8_SLOT;
 #pragma unroll
-        for (int j = 0; j < 2; ++j) OU_DMA16(xsrc[j] + 128 * cb, dst + 1024u * j);
+        for (int j = 0; j < 2; ++j) ADK_LDS_DMA16(xsrc[j] + 128 * cb, dst + 1024u * j);
     };
     constexpr int W2N = W2B / 8192;                        // W2 instructions per wave: 2 * MT2
     auto issue_w2 = [&]() __attribute__((always_inline)) {
         const unsigned char* g2 = reinterpret_cast<const unsigned char*>(a2.wfrag) + (size_t)tid * 16;
         const unsigned l2 = lds0 + (unsigned)W1B + (unsigned)wave * 1024u;
 #pragma unroll
-        for (int i = 0; i < W2N; ++i) OU_DMA16(g2 + 8192 * i, l2 + 8192u * i);
+        for (int i = 0; i < W2N; ++i) ADK_LDS_DMA16(g2 + 8192 * i, l2 + 8192u * i);
     };
     const float* b2l = reinterpret_cast<const float*>(stage0 + 256);
     const float* b1l = reinterpret_cast<const float*>(stage0 + 640);
@@ -193,16 +161,16 @@ __global__ __launch_bounds__(512, 2) void conv_ou16_w8_kernel(ConvArgs a1, ConvA
 
     if (!act) {
         OU_STAMP(1);
-        ou8_wait_vm<0>(); __syncthreads();                 // its pieces of W1 have landed
+        wait_vm<0>(); __syncthreads();                 // its pieces of W1 have landed
         OU_STAMP(2);
         issue_w2();
-        ou8_wait_vm<0>();
+        wait_vm<0>();
         OU_STAMP(3);
     } else {
         // ---- GEMM 1: c[m][t] = sum_k W1[m][k] x[k][t], 64 rows (four 16-row m-tiles) x this wave's 16 steps; one column block = one 32-k step ----
         issue_block(0); issue_block(1); issue_block(2);
         OU_STAMP(1);
-        f32x4m am[4], ac[4];
+        f32x4 am[4], ac[4];
 #pragma unroll
         for (int m = 0; m < 4; ++m)
 #pragma unroll
@@ -213,25 +181,19 @@ __global__ __launch_bounds__(512, 2) void conv_ou16_w8_kernel(ConvArgs a1, ConvA
 #pragma unroll
         for (int cb = 0; cb < OU_NCB; ++cb) {
             // in flight at most (12 issued up front, + 2 per block requested in the loop, + W2N behind block 5):
-            if (cb == 0) { ou8_wait_vm<4>(); __syncthreads(); }                 // {W1, block 0} landed here -- and, behind the barrier, everybody's W1
-            else if (cb == 1 || cb == 2) ou8_wait_vm<4>();
-            else if (cb == 3) ou8_wait_vm<4 + W2N>();                           // blocks 4, 5 and W2 may stay in flight
-            else if (cb == 4) ou8_wait_vm<2 + W2N>();
-            else ou8_wait_vm<W2N>();
+            if (cb == 0) { wait_vm<4>(); __syncthreads(); }                 // {W1, block 0} landed here -- and, behind the barrier, everybody's W1
+            else if (cb == 1 || cb == 2) wait_vm<4>();
+            else if (cb == 3) wait_vm<4 + W2N>();                           // blocks 4, 5 and W2 may stay in flight
+            else if (cb == 4) wait_vm<2 + W2N>();
+            else wait_vm<W2N>();
             if (cb == 0) {
                 OU_STAMP(2);
                 if (tid < OU_CM / 4) {                     // history row: activation, split, into the halo row of wave 0
                     const float4 hrow = *reinterpret_cast<const float4*>(stage0 + 16 * tid);
-                    const float x[4] = {hrow.x, hrow.y, hrow.z, hrow.w};
-                    f16x4u hi, lo;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float v = ou_act<ACT>(x[e], a2.slope);
-                        const _Float16 h = (_Float16)v;
-                        hi[e] = h; lo[e] = (_Float16)((v - (float)h) * kOuLoScale);
-                    }
-                    *reinterpret_cast<f16x4u*>(halo + 8 * tid) = hi;
-                    *reinterpret_cast<f16x4u*>(halo + 2 * OU_CM + 8 * tid) = lo;
+                    f16x4 hi, lo;
+                    act_split4<ACT>(hrow, a2.slope, hi, lo);
+                    *reinterpret_cast<f16x4*>(halo + 8 * tid) = hi;
+                    *reinterpret_cast<f16x4*>(halo + 2 * OU_CM + 8 * tid) = lo;
                 }
             }
             const unsigned char* xs = ring + (cb % 3) * OU8_SLOT + l15 * 128;
@@ -242,19 +204,14 @@ __global__ __launch_bounds__(512, 2) void conv_ou16_w8_kernel(ConvArgs a1, ConvA
                 issue_block(cb + 3);
                 if (cb + 3 == OU_NCB - 1) issue_w2();
             }
-            const float x[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-            f16x8u bh, bl;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const _Float16 h = (_Float16)x[e];
-                bh[e] = h; bl[e] = (_Float16)((x[e] - (float)h) * kOuLoScale);
-            }
-            f16x8u Ah[4], Al[4];
+            f16x8 bh, bl;
+            split8(x0, x1, bh, bl);
+            f16x8 Ah[4], Al[4];
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
                 const unsigned char* wp = w1l + (size_t)((m >> 1) * KS1 + 2 * cb) * 2048 + (m & 1) * 256 + a_lane;
-                Ah[m] = *reinterpret_cast<const f16x8u*>(wp);
-                Al[m] = *reinterpret_cast<const f16x8u*>(wp + 1024);
+                Ah[m] = *reinterpret_cast<const f16x8*>(wp);
+                Al[m] = *reinterpret_cast<const f16x8*>(wp + 1024);
             }
 #pragma unroll
             for (int m = 0; m < 4; ++m) am[m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[m], bh, am[m], 0, 0, 0);
@@ -263,7 +220,7 @@ __global__ __launch_bounds__(512, 2) void conv_ou16_w8_kernel(ConvArgs a1, ConvA
 #pragma unroll
             for (int m = 0; m < 4; ++m) ac[m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Al[m], bh, ac[m], 0, 0, 0);
         }
-        ou8_wait_vm<0>();                                  // W2
+        wait_vm<0>();                                  // W2
         OU_STAMP(3);
         // c (+ bias): act(c), split, over this wave's ring; the last step's raw row to `clast`; the row the NEXT wave's first step needs as
         // its older tap to that wave's halo row.  Lane (column l15, kg) holds channels 16 m + 4 kg + {0..3}.
@@ -274,25 +231,21 @@ __global__ __launch_bounds__(512, 2) void conv_ou16_w8_kernel(ConvArgs a1, ConvA
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
             const int ml = 16 * m + 4 * kg;
-            float v[4] = {fmaf(ac[m][0], kOuLoInv, am[m][0]), fmaf(ac[m][1], kOuLoInv, am[m][1]), fmaf(ac[m][2], kOuLoInv, am[m][2]), fmaf(ac[m][3], kOuLoInv, am[m][3])};
+            float v[4] = {join(am[m][0], ac[m][0]), join(am[m][1], ac[m][1]), join(am[m][2], ac[m][2]), join(am[m][3], ac[m][3])};
             chk = fmaf(v[0], 0.f, chk); chk = fmaf(v[1], 0.f, chk); chk = fmaf(v[2], 0.f, chk); chk = fmaf(v[3], 0.f, chk);
             if (a1.bias) {
                 const float4 bb = *reinterpret_cast<const float4*>(b1l + ml);
                 v[0] += bb.x; v[1] += bb.y; v[2] += bb.z; v[3] += bb.w;
             }
             if (is_last) *reinterpret_cast<float4*>(clast + ml) = make_float4(v[0], v[1], v[2], v[3]);
-            f16x4u hi, lo;
+            f16x4 hi, lo;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float y = ou_act<ACT>(v[e], a2.slope);
-                const _Float16 h = (_Float16)y;
-                hi[e] = h; lo[e] = (_Float16)((y - (float)h) * kOuLoScale);
-            }
-            *reinterpret_cast<f16x4u*>(lrow + 2 * ml) = hi;
-            *reinterpret_cast<f16x4u*>(lrow + 2 * OU_CM + 2 * ml) = lo;
+            for (int e = 0; e < 4; ++e) split_to(act_in<ACT>(v[e], a2.slope), hi, lo, e);
+            *reinterpret_cast<f16x4*>(lrow + 2 * ml) = hi;
+            *reinterpret_cast<f16x4*>(lrow + 2 * OU_CM + 2 * ml) = lo;
             if (to_halo) {
-                *reinterpret_cast<f16x4u*>(hrow2 + 2 * ml) = hi;
-                *reinterpret_cast<f16x4u*>(hrow2 + 2 * OU_CM + 2 * ml) = lo;
+                *reinterpret_cast<f16x4*>(hrow2 + 2 * ml) = hi;
+                *reinterpret_cast<f16x4*>(hrow2 + 2 * OU_CM + 2 * ml) = lo;
             }
         }
     }
@@ -305,19 +258,19 @@ __global__ __launch_bounds__(512, 2) void conv_ou16_w8_kernel(ConvArgs a1, ConvA
         orow0 %= a2.out_rows;
         const unsigned char* xr0 = (l15 == 0 ? halo + wave * OU8_RSC : ring + (l15 - 1) * OU8_RSC) + 16 * kg;
         const unsigned char* xr1 = ring + l15 * OU8_RSC + 16 * kg;
-        f16x8u bh[4], bl[4];
+        f16x8 bh[4], bl[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const unsigned char* p = (q >> 1 ? xr1 : xr0) + 64 * (q & 1);
-            bh[q] = *reinterpret_cast<const f16x8u*>(p);
-            bl[q] = *reinterpret_cast<const f16x8u*>(p + 2 * OU_CM);
+            bh[q] = *reinterpret_cast<const f16x8*>(p);
+            bl[q] = *reinterpret_cast<const f16x8*>(p + 2 * OU_CM);
         }
         const __amdgpu_buffer_rsrc_t rsrc_out = __builtin_amdgcn_make_buffer_rsrc(a2.out, 0, u.out_bytes, 0x00020000);
         const unsigned out_base = ((unsigned)b * (unsigned)a2.out_rows * (unsigned)a2.out_ch + (unsigned)a2.out_choff) * 4u;
         const unsigned row_bytes = (unsigned)a2.out_ch * 4u;
         const bool has_b2 = a2.bias != nullptr;
         const unsigned oob_mask = valid ? 0u : 0x80000000u;    // columns past the end: the store goes out of bounds (dropped), no branch
-        f32x4m am2[M2], ac2[M2];
+        f32x4 am2[M2], ac2[M2];
 #pragma unroll
         for (int m = 0; m < M2; ++m)
 #pragma unroll
@@ -328,8 +281,8 @@ __global__ __launch_bounds__(512, 2) void conv_ou16_w8_kernel(ConvArgs a1, ConvA
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const unsigned char* wp = w2l + (size_t)((m >> 1) * OU_KS2 + 2 * q) * 2048 + (m & 1) * 256 + a_lane;
-                    const f16x8u Ah = *reinterpret_cast<const f16x8u*>(wp);
-                    const f16x8u Al = *reinterpret_cast<const f16x8u*>(wp + 1024);
+                    const f16x8 Ah = *reinterpret_cast<const f16x8*>(wp);
+                    const f16x8 Al = *reinterpret_cast<const f16x8*>(wp + 1024);
                     am2[m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah, bh[q], am2[m], 0, 0, 0);
                     ac2[m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah, bl[q], ac2[m], 0, 0, 0);
                     ac2[m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Al, bh[q], ac2[m], 0, 0, 0);
@@ -338,8 +291,7 @@ __global__ __launch_bounds__(512, 2) void conv_ou16_w8_kernel(ConvArgs a1, ConvA
             if (m > 0) {
                 const int m1 = m - 1;                          // finish of the previous m-tile: GEMM rows 16 m1 + 4 kg + {0..3}
                 const int ml = 16 * m1 + 4 * kg;
-                float4 v = make_float4(fmaf(ac2[m1][0], kOuLoInv, am2[m1][0]), fmaf(ac2[m1][1], kOuLoInv, am2[m1][1]),
-                                       fmaf(ac2[m1][2], kOuLoInv, am2[m1][2]), fmaf(ac2[m1][3], kOuLoInv, am2[m1][3]));
+                float4 v = join4(am2[m1], ac2[m1]);
                 chk = fmaf(v.x, 0.f, chk); chk = fmaf(v.y, 0.f, chk); chk = fmaf(v.z, 0.f, chk); chk = fmaf(v.w, 0.f, chk);
                 float4 bb = *reinterpret_cast<const float4*>(b2l + ml);
                 bb.x = has_b2 ? bb.x : 0.f; bb.y = has_b2 ? bb.y : 0.f; bb.z = has_b2 ? bb.z : 0.f; bb.w = has_b2 ? bb.w : 0.f;
@@ -348,7 +300,7 @@ __global__ __launch_bounds__(512, 2) void conv_ou16_w8_kernel(ConvArgs a1, ConvA
                 int r2 = orow0 + ph;
                 if (r2 >= a2.out_rows) r2 -= a2.out_rows;
                 const unsigned off = (out_base + (unsigned)r2 * row_bytes + (unsigned)(ml - ph * a2.cout_real) * 4u) | oob_mask;
-                u32x4o pv;
+                u32x4 pv;
                 pv.x = __float_as_uint(v.x); pv.y = __float_as_uint(v.y); pv.z = __float_as_uint(v.z); pv.w = __float_as_uint(v.w);
                 // sc1 = write-through: the 64-byte pieces (four lanes per step and m-tile) leave the L2 while the launch runs instead of in its
                 // end-of-kernel write-back -- 11.3 -> 11.0 us by rocprofv3, nothing changes in the three-stream schedule (sessions r6_s27.sh,
@@ -366,8 +318,6 @@ __global__ __launch_bounds__(512, 2) void conv_ou16_w8_kernel(ConvArgs a1, ConvA
     if (!(chk == 0.f)) atomicOr(u.err, 8);
 }
 
-bool ou_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 // a1: the 1x1 conv into 64 channels, a2: the 2-tap polyphase transposed conv that reads exactly what a1 writes
@@ -379,8 +329,8 @@ bool conv_ou16_fusable(const ConvArgs& a1, const ConvArgs& a2) {
     if (a1.batch != a2.batch || a1.t_out != a2.t_out || a1.t_out < 1 || a1.t_out > OU_TMAX) return false;
     if (a2.in != a1.out || a2.in_rows != a1.out_rows || a2.in_ch != a1.out_ch || a2.in_choff != a1.out_choff) return false;
     if (a2.in_row0 != (a1.out_cursor + a1.out_rows - 1) % a1.out_rows) return false;    // one row of history, right in front of the new rows
-    if ((a1.in_ch % 4) || (a1.in_choff % 4) || (a1.out_ch % 4) || (a1.out_choff % 4) || !ou_aligned16(a1.in) || !ou_aligned16(a1.out) || !ou_aligned16(a1.wfrag)) return false;
-    if (a1.bias && !ou_aligned16(a1.bias)) return false;
+    if ((a1.in_ch % 4) || (a1.in_choff % 4) || (a1.out_ch % 4) || (a1.out_choff % 4) || !aligned16(a1.in) || !aligned16(a1.out) || !aligned16(a1.wfrag)) return false;
+    if (a1.bias && !aligned16(a1.bias)) return false;
     return true;
 }
 
@@ -414,9 +364,7 @@ int launch_conv_ou16(const ConvArgs& a1, const ConvArgs& a2, hipStream_t s) {
         if (mt2 == 2) return go(act, std::integral_constant<int, 2>());
         return go(act, std::integral_constant<int, 3>());
     };
-    if (a2.act_in == ADK_ACT_ELU) return by_mt(std::integral_constant<int, ADK_ACT_ELU>());
-    if (a2.act_in == ADK_ACT_LEAKY) return by_mt(std::integral_constant<int, ADK_ACT_LEAKY>());
-    return by_mt(std::integral_constant<int, ADK_ACT_NONE>());
+    return with_act_in(a2.act_in, nullptr, by_mt);
 }
 
 }  // namespace adk

@@ -28,8 +28,7 @@
 // frame share a 32-column MFMA tile (128-channel layers: 2 streams x 25 steps per workgroup).
 // Per output element the operations and their order are exactly those of conv_rl16 (k ascending, acc0 + acc1/2048, + bias,
 // + residual): the result is BIT-IDENTICAL to the per-op path (tests/test_gpu_b256.py::test_residual_chains_are_bit_identical).
-#include "adk_common.h"
-#include <type_traits>
+#include "conv_split16.h"      // the operand format, act_split / join4 / not_finite4, ADK_LDS_DMA16, wait_vm
 #include <cstdlib>
 
 #ifndef ADK_RB16_PF32
@@ -84,16 +83,9 @@ static int g_rb_launch = 0;
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4s __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kRbMaxConvs = 8;
 constexpr int kRbMaxHist = 56;           // rows of causal history a conv of the chain may need ((K-1) * dilation: 54 for K7 d9, 50 for K11 d5)
 constexpr int kRbTouchSink = 256;      // bytes at the end of the dynamic LDS that the L2 warm-up touches (LDS-DMA loads nobody reads) land in
-constexpr float kRbLoScale = 2048.f, kRbLoInv = 1.f / 2048.f;
 
 struct RbNode {                          // a tensor of the chain: where its rows live in HBM (a state ring)
     float* base; int rows, ch, cursor, choff, gstride;      // row of step t of stream b: base + (b * rows + (cursor + t) mod rows) * ch + choff + g * gstride
@@ -116,29 +108,11 @@ struct RbArgs {
     int dbg_slot;
 };
 
-template <int ACT>
-__device__ __forceinline__ float rb_act(float x, float slope) {
-    if (ACT == ADK_ACT_ELU) return x > 0.f ? x : expm1_neg(x);
-    if (ACT == ADK_ACT_LEAKY) return x > 0.f ? x : x * slope;
-    return x;
-}
-
-__device__ __forceinline__ f16x8 rb_as_f16x8(const u32x4s& v) {
-    union { u32x4s u; f16x8 h; } c; c.u = v; return c.h;
-}
-
 // 8 consecutive channels of one row: activation, split into hi / lo halves, into the row's LDS slots
 template <int C, int ACT>
 __device__ __forceinline__ void rb_put8(unsigned char* dst, const float4& u, const float4& v, float slope) {
-    const float x[8] = {u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
     f16x8 hi, lo;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float y = rb_act<ACT>(x[j], slope);
-        const _Float16 h = (_Float16)y;
-        hi[j] = h;
-        lo[j] = (_Float16)((y - (float)h) * kRbLoScale);
-    }
+    act_split8<ACT>(u, v, slope, hi, lo);
     *reinterpret_cast<f16x8*>(dst) = hi;
     *reinterpret_cast<f16x8*>(dst + 2 * C) = lo;
 }
@@ -149,7 +123,7 @@ __device__ __forceinline__ void rb_put8(unsigned char* dst, const float4& u, con
 template <int C, int TAPS, int PF, int LS, int NA, int NTW>
 __device__ __forceinline__ void rb_mfma(const unsigned char* const (&x)[NTW], int dil_rs,
                                         const __amdgpu_buffer_rsrc_t rsrc_w, unsigned lane16, unsigned wbase,
-                                        u32x4s (&ah)[PF + 1], u32x4s (&al)[PF + 1], f32x16 (&m)[NTW], f32x16 (&c)[NTW]) {
+                                        u32x4 (&ah)[PF + 1], u32x4 (&al)[PF + 1], f32x16 (&m)[NTW], f32x16 (&c)[NTW]) {
     constexpr int CH = C / 16, STEPS = TAPS * CH;
 #pragma unroll
     for (int s = 0; s < STEPS; ++s) {
@@ -164,7 +138,7 @@ __device__ __forceinline__ void rb_mfma(const unsigned char* const (&x)[NTW], in
         }
         const int tap = s / CH, ch = s - tap * CH;
         const int off = (ADK_RB16_DBG & 8) ? 0 : tap * dil_rs + 32 * ch;
-        const f16x8 Ah = rb_as_f16x8(ah[(ADK_RB16_DBG & 2) ? 0 : s % (PF + 1)]), Al = rb_as_f16x8(al[(ADK_RB16_DBG & 2) ? 0 : s % (PF + 1)]);
+        const f16x8 Ah = as_f16x8(ah[(ADK_RB16_DBG & 2) ? 0 : s % (PF + 1)]), Al = as_f16x8(al[(ADK_RB16_DBG & 2) ? 0 : s % (PF + 1)]);
         f16x8 bh[NA], bl[NA];
 #pragma unroll
         for (int j = 0; j < NA; ++j) {
@@ -208,9 +182,6 @@ struct RbRing {
     int sl;                         // slot of the next group to be consumed (0 .. WR-1)
 };
 
-#define RB_DMA16(gptr, m0val) do { unsigned m0_keep_; asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" \
-                                                            : "=&s"(m0_keep_) : "v"(gptr), "s"(m0val) : "memory"); } while (0)      /* M0 is the compiler's: put back */
-
 // groups [0, min(WR - 1, NG)) of a conv: requested ahead of its loop (gsrc: this lane's source of ITS piece of group 0)
 template <int C, int TAPS, int WR>
 __device__ __forceinline__ void rb_ring_preload(const RbRing& rg, const unsigned char* gsrc, int wave) {
@@ -218,7 +189,7 @@ __device__ __forceinline__ void rb_ring_preload(const RbRing& rg, const unsigned
     int sl = rg.sl;
 #pragma unroll
     for (int j = 0; j < PD; ++j) {
-        if (j < NG) RB_DMA16(gsrc + (size_t)j * GS * 2048u, rg.lds_addr + (unsigned)sl * 4096u + (unsigned)wave * 1024u);
+        if (j < NG) ADK_LDS_DMA16(gsrc + (size_t)j * GS * 2048u, rg.lds_addr + (unsigned)sl * 4096u + (unsigned)wave * 1024u);
         sl = sl + 1 == WR ? 0 : sl + 1;
     }
 }
@@ -241,7 +212,7 @@ __device__ __forceinline__ void rb_mfma_ring(const unsigned char* const (&x)[NTW
         else asm volatile("s_waitcnt vmcnt(3) lgkmcnt(0)\n\ts_barrier" ::: "memory");
         if (i + PD < NG) {
             const int dst = rg.sl + PD >= WR ? rg.sl + PD - WR : rg.sl + PD;
-            RB_DMA16(gsrc + (size_t)(i + PD) * GS * 2048u, rg.lds_addr + (unsigned)dst * 4096u + (unsigned)wave * 1024u);
+            ADK_LDS_DMA16(gsrc + (size_t)(i + PD) * GS * 2048u, rg.lds_addr + (unsigned)dst * 4096u + (unsigned)wave * 1024u);
         }
         __builtin_amdgcn_sched_barrier(0);
         const unsigned char* slot = rg.base + rg.sl * 4096 + lane16;
@@ -305,8 +276,7 @@ __global__ __launch_bounds__(256, WPS) void conv_rb16_kernel(RbArgs r) {
         const int pad = (r.n_main + 7) & ~7;
         if (r.helpers <= 0 || (int)blockIdx.x < pad) return;
         const int h = (int)blockIdx.x - pad, xcd = h & 7, sub = h >> 3;
-        typedef unsigned char __attribute__((address_space(3)))* lds_u8h_t;
-        const unsigned sink = (unsigned)(size_t)(lds_u8h_t)xs;
+        const unsigned sink = (unsigned)(size_t)(lds_u8_t)xs;
         unsigned seen = 0;                                   // groups whose workgroups sit on this XCD (groups <= 32 here: the host checked)
         for (int i = xcd; i < r.n_main; i += 8) seen |= 1u << (i % r.groups);
         auto touch = [&](const unsigned char* ptr) __attribute__((always_inline)) {
@@ -343,7 +313,7 @@ __global__ __launch_bounds__(256, WPS) void conv_rb16_kernel(RbArgs r) {
                 for (int line = sub * NT + tid; line < nlines; line += r.helpers * NT) touch(wb + (size_t)line * 128u);
             }
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the sink is this workgroup's LDS: nothing may still be landing when it is released
+        wait_vm<0>();                                        // the sink is this workgroup's LDS: nothing may still be landing when it is released
         return;
     }
     RB_STAMP(0);
@@ -376,8 +346,7 @@ __global__ __launch_bounds__(256, WPS) void conv_rb16_kernel(RbArgs r) {
     }
 
     // ---- first weight fragments of conv 0: issued before anything else (their L2 round trip overlaps the staging) ----
-    u32x4s ah[PF + 1], al[PF + 1];
-    typedef unsigned char __attribute__((address_space(3)))* lds_u8_t;
+    u32x4 ah[PF + 1], al[PF + 1];
     // the weight ring (WR > 0) sits behind the rows and the bias block; this wave's DMA piece of every group: half (hi / lo) = wave & 1,
     // (step in group, m-tile) = wave >> 1 -- 32 channels: step; 64 channels: m-tile
     const unsigned ring_off = (unsigned)r.spw * (unsigned)r.rps * (unsigned)RS + (BIAS_LDS ? (unsigned)r.n_convs * C * 4u : 0u);
@@ -548,11 +517,10 @@ __global__ __launch_bounds__(256, WPS) void conv_rb16_kernel(RbArgs r) {
         for (int qd = 0; qd < 4; ++qd) {
             float4 bb = breg[qd];
             if constexpr (BIAS_LDS) bb = *reinterpret_cast<const float4*>(bias_lds + k * C + mt * 32 + 8 * qd + 4 * lh);
-            float v0 = fmaf(ac[4 * qd], kRbLoInv, am[4 * qd]), v1 = fmaf(ac[4 * qd + 1], kRbLoInv, am[4 * qd + 1]);
-            float v2 = fmaf(ac[4 * qd + 2], kRbLoInv, am[4 * qd + 2]), v3 = fmaf(ac[4 * qd + 3], kRbLoInv, am[4 * qd + 3]);
-            bad |= vld & (!(fabsf(v0) <= 3.0e38f) | !(fabsf(v1) <= 3.0e38f) | !(fabsf(v2) <= 3.0e38f) | !(fabsf(v3) <= 3.0e38f));
-            if (hb) { v0 += bb.x; v1 += bb.y; v2 += bb.z; v3 += bb.w; }
-            h[4 * qd] = v0; h[4 * qd + 1] = v1; h[4 * qd + 2] = v2; h[4 * qd + 3] = v3;
+            float4 v = join4(am, ac, qd);
+            bad |= vld & not_finite4(v);
+            if (hb) { v.x += bb.x; v.y += bb.y; v.z += bb.z; v.w += bb.w; }
+            h[4 * qd] = v.x; h[4 * qd + 1] = v.y; h[4 * qd + 2] = v.z; h[4 * qd + 3] = v.w;
         }
     };
     // rows of node k that later calls need (or all of them): straight from registers, raw f32
@@ -589,12 +557,7 @@ __global__ __launch_bounds__(256, WPS) void conv_rb16_kernel(RbArgs r) {
             const int ml = mt * 32 + 8 * qd + 4 * lh;
             f16x4 hi, lo;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float y = rb_act<ACT>(h[4 * qd + e], r.slope);
-                const _Float16 hh = (_Float16)y;
-                hi[e] = hh;
-                lo[e] = (_Float16)((y - (float)hh) * kRbLoScale);
-            }
+            for (int e = 0; e < 4; ++e) split_to(act_in<ACT>(h[4 * qd + e], r.slope), hi, lo, e);
             *reinterpret_cast<f16x4*>(row + 2 * ml) = hi;
             *reinterpret_cast<f16x4*>(row + 2 * C + 2 * ml) = lo;
         }
@@ -777,8 +740,6 @@ bool rb_plan(const ConvArgs* c, int n, RbPlan& pl) {
     pl.blocks = (long long)((a0.batch + pl.spw - 1) / pl.spw) * a0.groups;
     return pl.blocks <= 0x7fffffffLL;
 }
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 

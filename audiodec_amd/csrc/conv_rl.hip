@@ -11,13 +11,9 @@
 //   ahead) x B fragment (ds_read_b128 at row t + tap*dilation) -> 4 MFMAs per accumulator.
 // Waves split the (m-tile, n-tile) pairs of the tile; the split is rotated by the workgroup index so
 // the SIMDs of a CU that hosts several workgroups get equal shares.
-#include "adk_common.h"
-#include <type_traits>
+#include "conv_split16.h"      // act_in, buf_load4, the vector typedefs, with_act_in
 
 namespace adk {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4r __attribute__((ext_vector_type(4)));
 
 struct RlArgs {
     int tt;               // time-tile length (output steps per workgroup), multiple of 32 unless one tile covers t_out
@@ -27,18 +23,6 @@ struct RlArgs {
     int span;             // (taps-1)*dilation history rows in front of a tile
     unsigned w_bytes;
 };
-
-__device__ __forceinline__ float4 rl_load4(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff) {
-    const u32x4r v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 0);
-    return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-}
-
-template <int ACT>
-__device__ __forceinline__ float rl_act(float x, float slope) {
-    if (ACT == ADK_ACT_ELU) return x > 0.f ? x : expm1_neg(x);
-    if (ACT == ADK_ACT_LEAKY) return x > 0.f ? x : x * slope;
-    return x;
-}
 
 template <int C, int ACT, int TAPS>
 __global__ __launch_bounds__(256, 3) void conv_rl_kernel(ConvArgs a, RlArgs rl) {
@@ -72,8 +56,8 @@ __global__ __launch_bounds__(256, 3) void conv_rl_kernel(ConvArgs a, RlArgs rl) 
                 int row = a.in_row0 + t0 + rr;
                 row %= a.in_rows;
                 v = *reinterpret_cast<const float4*>(xin + (size_t)row * a.in_ch + 4 * c4);
-                v.x = rl_act<ACT>(v.x, a.slope); v.y = rl_act<ACT>(v.y, a.slope);
-                v.z = rl_act<ACT>(v.z, a.slope); v.w = rl_act<ACT>(v.w, a.slope);
+                v.x = act_in<ACT>(v.x, a.slope); v.y = act_in<ACT>(v.y, a.slope);
+                v.z = act_in<ACT>(v.z, a.slope); v.w = act_in<ACT>(v.w, a.slope);
             }
             *reinterpret_cast<float4*>(xs + rr * LD + 4 * c4) = v;
         }
@@ -105,12 +89,12 @@ __global__ __launch_bounds__(256, 3) void conv_rl_kernel(ConvArgs a, RlArgs rl) 
         // vmcnt(0) at the loop header and serialises every tap behind an L2 round trip).
         float4 af[2][KG];
 #pragma unroll
-        for (int q = 0; q < KG; ++q) af[0][q] = rl_load4(rsrc_w, lane16, wbase + (unsigned)q * 1024u);
+        for (int q = 0; q < KG; ++q) af[0][q] = buf_load4(rsrc_w, lane16, wbase + (unsigned)q * 1024u);
 #pragma unroll
         for (int tap = 0; tap < TAPS; ++tap) {
             if (tap + 1 < TAPS) {
 #pragma unroll
-                for (int q = 0; q < KG; ++q) af[(tap + 1) & 1][q] = rl_load4(rsrc_w, lane16, wbase + (unsigned)((tap + 1) * KG + q) * 1024u);
+                for (int q = 0; q < KG; ++q) af[(tap + 1) & 1][q] = buf_load4(rsrc_w, lane16, wbase + (unsigned)((tap + 1) * KG + q) * 1024u);
             }
             const int roff = tap * a.dilation * LD;
 #pragma unroll
@@ -226,10 +210,7 @@ int launch_rl(const ConvArgs& a, hipStream_t s) {
         if (a.taps == 7) return go(conv_rl_kernel<C, ACT, 7>);
         return go(conv_rl_kernel<C, ACT, 11>);
     };
-    if (a.act_in == ADK_ACT_ELU) return by_taps(std::integral_constant<int, ADK_ACT_ELU>());
-    if (a.act_in == ADK_ACT_LEAKY) return by_taps(std::integral_constant<int, ADK_ACT_LEAKY>());
-    if (a.act_in == ADK_ACT_NONE) return by_taps(std::integral_constant<int, ADK_ACT_NONE>());
-    return fail(ADK_ERR_ARG, "conv: unsupported input activation for the rows-in-LDS kernel");
+    return with_act_in(a.act_in, "conv: unsupported input activation for the rows-in-LDS kernel", by_taps);
 }
 }  // namespace
 

@@ -1,18 +1,9 @@
 // "Rows in LDS" causal conv with SPLIT-f16 operands on the f16 matrix cores (opt-in, ADK_IMPL_SPLIT16 / ADK_IMPL_SPLIT16_ROWS).
 //
-// Same structure as conv_rl.hip (one workgroup = one (stream, group, time tile), rows + history staged once),
-// but every f32 operand is carried as two f16 numbers
-//     v = hi + lo / 2048,   hi = f16(v),   lo = f16((v - hi) * 2048)          (22+ significant bits)
-// and a product sum is formed from three v_mfma_f32_32x32x16_f16 per 16 k:
-//     acc0 += A_hi * B_hi          acc1 += A_hi * B_lo + A_lo * B_hi          result = acc0 + acc1 / 2048
-// f16 x f16 products are exact in the f32 accumulator, so the only errors are the dropped lo*lo term
-// (2^-22 relative) and the 2^-22 representation error of each operand -- measured on gfx950 against fp64
-// (tools/mfma_f16_probe.hip, profiles/r1_f16_split_probe.txt): max |err| / sum|a b| = 8e-8 for K = 352..2816,
-// BELOW the 2e-7 of the f32 MFMA chain (which rounds after every product), at 3/16 of its matrix-core time.
-// f16 subnormal inputs are honoured by the instruction (same probe); |v| > 65504 overflows hi to inf, which makes every
-// output it feeds non-finite -- the epilogue tests its outputs and raises device flag bit 3 (adk_debug_flags).  Weights come pre-split in fragment order (adk_pack_weights_split16).
-#include "adk_common.h"
-#include <type_traits>
+// Same structure as conv_rl.hip (one workgroup = one (stream, group, time tile), rows + history staged once), with every f32
+// operand carried as two f16 numbers and three v_mfma_f32_32x32x16_f16 per 16 k: the format, its error and its overflow
+// check are described in conv_split16.h.
+#include "conv_split16.h"
 #include <cstdlib>
 
 #ifndef ADK_RL16_DBG
@@ -30,10 +21,6 @@ extern "C" int adk_debug_rl_wg_trace(unsigned long long* out, int n) {
 }
 #endif
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4s __attribute__((ext_vector_type(4)));
-
 struct Rl16Args {
     int tt;               // time-tile length (output steps per workgroup)
     int tiles_per_stream;
@@ -49,29 +36,6 @@ struct Rl16Args {
     const float* res2; int res2_rows, res2_ch, res2_cursor, res2_choff;
     int act_out2;
 };
-
-constexpr float kLoScale = 2048.f, kLoInv = 1.f / 2048.f;
-
-template <int ACT>
-__device__ __forceinline__ float rl16_act(float x, float slope) {
-    if (ACT == ADK_ACT_ELU) return x > 0.f ? x : expm1_neg(x);
-    if (ACT == ADK_ACT_LEAKY) return x > 0.f ? x : x * slope;
-    return x;
-}
-
-__device__ __forceinline__ void split8(const float4& u, const float4& v, f16x8& hi, f16x8& lo) {
-    const float x[8] = {u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const _Float16 h = (_Float16)x[j];
-        hi[j] = h;
-        lo[j] = (_Float16)((x[j] - (float)h) * kLoScale);
-    }
-}
-
-__device__ __forceinline__ f16x8 as_f16x8(const u32x4s& v) {
-    union { u32x4s u; f16x8 h; } c; c.u = v; return c.h;
-}
 
 // NW waves per workgroup; each wave owns work items (m-tile, pair of consecutive n-tiles) and keeps each
 // weight fragment in registers for both n-tiles.  PF = weight prefetch distance in 16-k chunks.
@@ -113,7 +77,7 @@ __global__ __launch_bounds__(64 * NW, ((PF > 4 || PF >= TAPS * C / 16) ? 2 : 3))
     const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.wfrag), 0, rl.w_bytes, 0x00020000);
     const unsigned lane16 = (unsigned)lane * 16u;
     const int rot = (wave + blockIdx.x + (blockIdx.x >> 8)) % NW;
-    u32x4s ah[PF + 1], al[PF + 1];
+    u32x4 ah[PF + 1], al[PF + 1];
     auto preload = [&](unsigned wb) {
 #pragma unroll
         for (int s = 0; s < PF && s < STEPS; ++s) {
@@ -138,7 +102,7 @@ __global__ __launch_bounds__(64 * NW, ((PF > 4 || PF >= TAPS * C / 16) ? 2 : 3))
 
     // FUSE: all fragments of the 1x1 conv for this wave's m-tile (C/16 chunks), fetched in the same round trip
     constexpr int ST2 = FUSE ? C / 16 : 1;
-    u32x4s a2h[ST2], a2l[ST2];
+    u32x4 a2h[ST2], a2l[ST2];
     if constexpr (FUSE) {
         constexpr int KS2 = (C + 63) / 64 * 4;         // chunks per m-tile in the packed layout (K padded to a multiple of 64)
         const __amdgpu_buffer_rsrc_t rsrc_w2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(rl.w2), 0, (unsigned)((C / 32) * KS2 * 2048), 0x00020000);
@@ -178,10 +142,10 @@ __global__ __launch_bounds__(64 * NW, ((PF > 4 || PF >= TAPS * C / 16) ? 2 : 3))
             for (int k = 0; k < SB; ++k) {
                 if (i0 + k * NT >= items) break;
                 float4 uu = u[k], vv = v[k];
-                uu.x = rl16_act<ACT>(uu.x, a.slope); uu.y = rl16_act<ACT>(uu.y, a.slope);
-                uu.z = rl16_act<ACT>(uu.z, a.slope); uu.w = rl16_act<ACT>(uu.w, a.slope);
-                vv.x = rl16_act<ACT>(vv.x, a.slope); vv.y = rl16_act<ACT>(vv.y, a.slope);
-                vv.z = rl16_act<ACT>(vv.z, a.slope); vv.w = rl16_act<ACT>(vv.w, a.slope);
+                uu.x = act_in<ACT>(uu.x, a.slope); uu.y = act_in<ACT>(uu.y, a.slope);
+                uu.z = act_in<ACT>(uu.z, a.slope); uu.w = act_in<ACT>(uu.w, a.slope);
+                vv.x = act_in<ACT>(vv.x, a.slope); vv.y = act_in<ACT>(vv.y, a.slope);
+                vv.z = act_in<ACT>(vv.z, a.slope); vv.w = act_in<ACT>(vv.w, a.slope);
                 f16x8 hi, lo;
                 split8(uu, vv, hi, lo);
                 unsigned char* d = xs + rr[k] * RS + 16 * c8[k];
@@ -266,9 +230,8 @@ __global__ __launch_bounds__(64 * NW, ((PF > 4 || PF >= TAPS * C / 16) ? 2 : 3))
             for (int qd = 0; qd < 4; ++qd) {
                 const int ml = mt * 32 + 8 * qd + 4 * lh;
                 if (ml >= a.cout_g) continue;
-                float4 v = make_float4(fmaf(ac[4 * qd], kLoInv, am[4 * qd]), fmaf(ac[4 * qd + 1], kLoInv, am[4 * qd + 1]),
-                                       fmaf(ac[4 * qd + 2], kLoInv, am[4 * qd + 2]), fmaf(ac[4 * qd + 3], kLoInv, am[4 * qd + 3]));
-                bad |= !(fabsf(v.x) <= 3.0e38f) | !(fabsf(v.y) <= 3.0e38f) | !(fabsf(v.z) <= 3.0e38f) | !(fabsf(v.w) <= 3.0e38f);
+                float4 v = join4(am, ac, qd);
+                bad |= not_finite4(v);
                 if (a.bias) {
                     const float4 bb = (EARLY_BIAS && item == rot) ? bias0[EARLY_BIAS ? qd : 0] : *reinterpret_cast<const float4*>(a.bias + g * a.cout_g + ml);
                     v.x += bb.x; v.y += bb.y; v.z += bb.z; v.w += bb.w;
@@ -308,24 +271,16 @@ __global__ __launch_bounds__(64 * NW, ((PF > 4 || PF >= TAPS * C / 16) ? 2 : 3))
 #pragma unroll
                 for (int qd = 0; qd < 4; ++qd) {
                     const int ml = mt * 32 + 8 * qd + 4 * lh;
-                    float h[4] = {fmaf(ac[4 * qd], kLoInv, am[4 * qd]), fmaf(ac[4 * qd + 1], kLoInv, am[4 * qd + 1]),
-                                  fmaf(ac[4 * qd + 2], kLoInv, am[4 * qd + 2]), fmaf(ac[4 * qd + 3], kLoInv, am[4 * qd + 3])};
-                    bad |= !(fabsf(h[0]) <= 3.0e38f) | !(fabsf(h[1]) <= 3.0e38f) | !(fabsf(h[2]) <= 3.0e38f) | !(fabsf(h[3]) <= 3.0e38f);
+                    float h[4] = {join(am[4 * qd], ac[4 * qd]), join(am[4 * qd + 1], ac[4 * qd + 1]), join(am[4 * qd + 2], ac[4 * qd + 2]), join(am[4 * qd + 3], ac[4 * qd + 3])};
+                    bad |= not_finite(h[0]) | not_finite(h[1]) | not_finite(h[2]) | not_finite(h[3]);
                     if (a.bias) {
                         const float4 bb = *reinterpret_cast<const float4*>(a.bias + g * a.cout_g + ml);
                         h[0] += bb.x; h[1] += bb.y; h[2] += bb.z; h[3] += bb.w;
                     }
-                    typedef _Float16 f16x4r __attribute__((ext_vector_type(4)));
-                    f16x4r hi, lo;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float y = rl16_act<ACT>(h[e], a.slope);
-                        const _Float16 hh = (_Float16)y;
-                        hi[e] = hh;
-                        lo[e] = (_Float16)((y - (float)hh) * kLoScale);
-                    }
-                    *reinterpret_cast<f16x4r*>(row + 2 * ml) = hi;
-                    *reinterpret_cast<f16x4r*>(row + 2 * C + 2 * ml) = lo;
+                    f16x4 hi, lo;
+                    act_split<ACT>(h, a.slope, hi, lo);
+                    *reinterpret_cast<f16x4*>(row + 2 * ml) = hi;
+                    *reinterpret_cast<f16x4*>(row + 2 * C + 2 * ml) = lo;
                 }
             }
         }
@@ -375,9 +330,8 @@ __global__ __launch_bounds__(64 * NW, ((PF > 4 || PF >= TAPS * C / 16) ? 2 : 3))
 #pragma unroll
                 for (int qd = 0; qd < 4; ++qd) {
                     const int ml = mt * 32 + 8 * qd + 4 * lh;
-                    float4 v = make_float4(fmaf(ac[4 * qd], kLoInv, am[4 * qd]), fmaf(ac[4 * qd + 1], kLoInv, am[4 * qd + 1]),
-                                           fmaf(ac[4 * qd + 2], kLoInv, am[4 * qd + 2]), fmaf(ac[4 * qd + 3], kLoInv, am[4 * qd + 3]));
-                    bad |= !(fabsf(v.x) <= 3.0e38f) | !(fabsf(v.y) <= 3.0e38f) | !(fabsf(v.z) <= 3.0e38f) | !(fabsf(v.w) <= 3.0e38f);
+                    float4 v = join4(am, ac, qd);
+                    bad |= not_finite4(v);
                     if (rl.bias2) {
                         const float4 bb = *reinterpret_cast<const float4*>(rl.bias2 + ml);
                         v.x += bb.x; v.y += bb.y; v.z += bb.z; v.w += bb.w;
@@ -423,7 +377,7 @@ __global__ __launch_bounds__(256) void pack_split16_kernel(const float* __restri
         float v = 0.f;
         if (m < cout_g && k < ktot) v = w[((size_t)g * cout_g + m) * ktot + k];
         const _Float16 hi = (_Float16)v;
-        const _Float16 lo = (_Float16)((v - (float)hi) * kLoScale);
+        const _Float16 lo = lo_part(v, hi);
         bad |= fabsf(v) > 65504.f;
         _Float16* o = out + blk * 1024 + lane * 8 + j;
         o[0] = hi; o[512] = lo;
@@ -446,12 +400,7 @@ bool conv_rl16_supported(const ConvArgs& a) {
     if (a.up != 1 && (a.taps != 2 || a.groups != 1 || a.cout_real % 4 || a.res)) return false;   // transposed convs: 2 taps, polyphase rows
     if (a.taps != 1 && a.taps != 2 && a.taps != 3 && a.taps != 7 && a.taps != 11) return false;   // tap loop unrolled at compile time
     if (a.cout_g % 32 != 0) return false;
-    if ((a.in_ch % 4) || (a.in_choff % 4) || (a.in_gstride % 4) || (a.out_ch % 4) || (a.out_choff % 4)) return false;
-    if (a.res && ((a.res_ch % 4) || (a.res_choff % 4) || (a.res_gstride % 4))) return false;
-    if ((reinterpret_cast<uintptr_t>(a.in) | reinterpret_cast<uintptr_t>(a.out) | reinterpret_cast<uintptr_t>(a.wfrag)) & 15) return false;
-    if (a.res && (reinterpret_cast<uintptr_t>(a.res) & 15)) return false;
-    if (a.bias && (reinterpret_cast<uintptr_t>(a.bias) & 15)) return false;
-    return true;
+    return conv_io_aligned(a);
 }
 
 static bool rl16_few_streams() {                 // ADK_RL16_FEW=0 (tuning): the round-1 rule -- rows kernel only when >= 192 long tiles
@@ -497,9 +446,8 @@ bool conv_rl16_preferred(const ConvArgs& a) {
 }
 
 namespace {
-template <int C, int NW>
-int launch_rl16(const ConvArgs& a, hipStream_t s, int tt) {
-    Rl16Args rl;
+// what the two launchers below have in common: the K-tap conv's part of Rl16Args; returns the dynamic LDS of the launch (C = channels per group)
+size_t rl16_fill(const ConvArgs& a, int tt, int C, Rl16Args& rl) {
     rl.span = (a.taps - 1) * a.dilation;
     rl.mt32_per_g = a.cout_g / 32;
     rl.ksteps = (a.ktot + 63) / 64 * 4;
@@ -507,9 +455,14 @@ int launch_rl16(const ConvArgs& a, hipStream_t s, int tt) {
     rl.err = conv_err_word(a);
     rl.tt = tt;
     rl.tiles_per_stream = (a.t_out + tt - 1) / tt;
-    constexpr int RS = 4 * C + 16;
     const int tt_pad = (std::min(tt, a.t_out) + 31) / 32 * 32;
-    const size_t lds = (size_t)(rl.span + tt_pad) * RS;
+    return (size_t)(rl.span + tt_pad) * (4 * C + 16);       // rows of [C halfs hi][C halfs lo][16 B pad]
+}
+
+template <int C, int NW>
+int launch_rl16(const ConvArgs& a, hipStream_t s, int tt) {
+    Rl16Args rl;
+    const size_t lds = rl16_fill(a, tt, C, rl);
     const long long blocks = (long long)a.batch * rl.tiles_per_stream * a.groups;
     if (blocks > 0x7fffffffLL) return fail(ADK_ERR_SHAPE, "conv: too many workgroups");
     if (lds > 64 * 1024) return fail(ADK_ERR_SHAPE, "conv: rows-in-LDS tile exceeds 64 KiB");
@@ -531,10 +484,7 @@ int launch_rl16(const ConvArgs& a, hipStream_t s, int tt) {
         if (a.taps == 7) return go(conv_rl16_kernel<C, ACT, 7, NW, PF>);
         return go(conv_rl16_kernel<C, ACT, 11, NW, PF>);
     };
-    if (a.act_in == ADK_ACT_ELU) return by_taps(std::integral_constant<int, ADK_ACT_ELU>());
-    if (a.act_in == ADK_ACT_LEAKY) return by_taps(std::integral_constant<int, ADK_ACT_LEAKY>());
-    if (a.act_in == ADK_ACT_NONE) return by_taps(std::integral_constant<int, ADK_ACT_NONE>());
-    return fail(ADK_ERR_ARG, "conv: unsupported input activation for the rows-in-LDS kernel");
+    return with_act_in(a.act_in, "conv: unsupported input activation for the rows-in-LDS kernel", by_taps);
 }
 }  // namespace
 
@@ -560,9 +510,9 @@ bool conv_rl16_fusable(const ConvArgs& a1, const ConvArgs& a2) {
     if (a2.cin_g != a1.cout_g || a2.cout_g != a1.cout_g || a1.cin_g != a1.cout_g) return false;          // C -> C -> C
     if (a2.act_in != a1.act_in || a2.slope != a1.slope || a2.batch != a1.batch || a2.t_out != a1.t_out) return false;
     if (a2.in != a1.out || a2.in_rows != a1.out_rows || a2.in_ch != a1.out_ch || a2.in_choff != a1.out_choff) return false;   // h feeds only the 1x1
-    if ((a2.out_ch % 4) || (a2.out_choff % 4) || (reinterpret_cast<uintptr_t>(a2.out) & 15) || (reinterpret_cast<uintptr_t>(a2.wfrag) & 15)) return false;
-    if (a2.res && ((a2.res_ch % 4) || (a2.res_choff % 4) || (reinterpret_cast<uintptr_t>(a2.res) & 15))) return false;
-    if (a2.bias && (reinterpret_cast<uintptr_t>(a2.bias) & 15)) return false;
+    if ((a2.out_ch % 4) || (a2.out_choff % 4) || !aligned16(a2.out) || !aligned16(a2.wfrag)) return false;
+    if (a2.res && ((a2.res_ch % 4) || (a2.res_choff % 4) || !aligned16(a2.res))) return false;
+    if (a2.bias && !aligned16(a2.bias)) return false;
     return true;
 }
 
@@ -570,30 +520,18 @@ namespace {
 template <int C, int NW>
 int launch_rl16_fused(const ConvArgs& a, const ConvArgs& a2, hipStream_t s, int tt) {
     Rl16Args rl;
-    rl.span = (a.taps - 1) * a.dilation;
-    rl.mt32_per_g = a.cout_g / 32;
-    rl.ksteps = (a.ktot + 63) / 64 * 4;
-    rl.w_bytes = (unsigned)((unsigned long long)a.groups * rl.mt32_per_g * rl.ksteps * 2048ull);
-    rl.err = conv_err_word(a);
-    rl.tt = tt;
-    rl.tiles_per_stream = (a.t_out + tt - 1) / tt;
+    const size_t lds = rl16_fill(a, tt, C, rl);
     rl.w2 = a2.wfrag; rl.bias2 = a2.bias;
     rl.out2 = a2.out; rl.out2_rows = a2.out_rows; rl.out2_ch = a2.out_ch; rl.out2_cursor = a2.out_cursor; rl.out2_choff = a2.out_choff;
     rl.res2 = a2.res; rl.res2_rows = a2.res_rows; rl.res2_ch = a2.res_ch; rl.res2_cursor = a2.res_cursor; rl.res2_choff = a2.res_choff;
     rl.act_out2 = a2.act_out;
-    constexpr int RS = 4 * C + 16;
-    const int tt_pad = (std::min(tt, a.t_out) + 31) / 32 * 32;
-    const size_t lds = (size_t)(rl.span + tt_pad) * RS;
     const long long blocks = (long long)a.batch * rl.tiles_per_stream;
     if (blocks > 0x7fffffffLL || lds > 64 * 1024) return fail(ADK_ERR_SHAPE, "conv: fused residual unit does not fit");
-    auto go = [&](auto kern) -> int {
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * NW), lds, s, a, rl);
+    return with_act_in(a.act_in, nullptr, [&](auto act) -> int {
+        hipLaunchKernelGGL((conv_rl16_kernel<C, decltype(act)::value, 7, NW, 2, true>), dim3((unsigned)blocks), dim3(64 * NW), lds, s, a, rl);
         ADK_HIP_CHECK(hipGetLastError());
         return ADK_OK;
-    };
-    if (a.act_in == ADK_ACT_ELU) return go(conv_rl16_kernel<C, ADK_ACT_ELU, 7, NW, 2, true>);
-    if (a.act_in == ADK_ACT_LEAKY) return go(conv_rl16_kernel<C, ADK_ACT_LEAKY, 7, NW, 2, true>);
-    return go(conv_rl16_kernel<C, ADK_ACT_NONE, 7, NW, 2, true>);
+    });
 }
 }  // namespace
 

@@ -16,28 +16,15 @@
 //     adk_pack_weights_split16 layout, conflict-free b128 reads) and shared by the four waves; the single barrier is passed
 //     while the activation loads are still in flight;
 //   * outputs leave as 16-byte stores, the 3 phases of a time step fill one contiguous 384-byte span.
-#include "adk_common.h"
-#include <type_traits>
+// Operand format, act_split8, join4, not_finite4, wait_vm: conv_split16.h.
+#include "conv_split16.h"
 
 namespace adk {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8u __attribute__((ext_vector_type(8)));
-
 namespace {
-constexpr float kUpLoScale = 2048.f, kUpLoInv = 1.f / 2048.f;
 constexpr int UP_CIN = 64, UP_KSTEPS = 2 * UP_CIN / 16;          // 2 taps x 64 channels = 128 k = 8 chunks of 16
 
-template <int ACT>
-__device__ __forceinline__ float up_act(float x, float slope) {
-    if (ACT == ADK_ACT_ELU) return x > 0.f ? x : expm1_neg(x);
-    if (ACT == ADK_ACT_LEAKY) return x > 0.f ? x : x * slope;
-    return x;
-}
-
 struct UpArgs { int chunks_per_stream; int m_tiles; float inv_cout_real; int* err; };
-typedef const void __attribute__((address_space(1)))* gptr_t;
-typedef void __attribute__((address_space(3)))* lptr_t;
 
 template <int ACT, int MT>
 __global__ __launch_bounds__(256, 2) void conv_up16_kernel(ConvArgs a, UpArgs u) {
@@ -86,21 +73,12 @@ __global__ __launch_bounds__(256, 2) void conv_up16_kernel(ConvArgs a, UpArgs u)
     if (tid < 32 * MT) blds[tid] = bias_v;
     // every wave's LDS-DMA slice is read by the OTHER waves: drain this wave's VM-counted DMA explicitly before the barrier that
     // publishes it (hipcc 7.2 happens to emit the wait for the workgroup fence; the fence does not formally promise it)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     __syncthreads();                                        // the weights of all waves are in LDS (and the loads above have landed: one round trip for all)
     if (!live) return;
 
-    f16x8u bh[UP_KSTEPS], bl[UP_KSTEPS];
-    auto convert = [&](int s) {
-        const float x[8] = {xr[s][0].x, xr[s][0].y, xr[s][0].z, xr[s][0].w, xr[s][1].x, xr[s][1].y, xr[s][1].z, xr[s][1].w};
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float v = up_act<ACT>(x[e], a.slope);
-            const _Float16 h = (_Float16)v;
-            bh[s][e] = h;
-            bl[s][e] = (_Float16)((v - (float)h) * kUpLoScale);
-        }
-    };
+    f16x8 bh[UP_KSTEPS], bl[UP_KSTEPS];
+    auto convert = [&](int s) { act_split8<ACT>(xr[s][0], xr[s][1], a.slope, bh[s], bl[s]); };
 
     float* outb = a.out + (size_t)b * a.out_rows * a.out_ch + a.out_choff;
     int orow0 = a.out_cursor + t * a.up;
@@ -115,8 +93,8 @@ __global__ __launch_bounds__(256, 2) void conv_up16_kernel(ConvArgs a, UpArgs u)
         const unsigned char* wp = wlds + (size_t)mt * UP_KSTEPS * 2048 + lane * 16;
 #pragma unroll
         for (int s = 0; s < UP_KSTEPS; ++s) {
-            const f16x8u Ah = *reinterpret_cast<const f16x8u*>(wp + s * 2048);
-            const f16x8u Al = *reinterpret_cast<const f16x8u*>(wp + s * 2048 + 1024);
+            const f16x8 Ah = *reinterpret_cast<const f16x8*>(wp + s * 2048);
+            const f16x8 Al = *reinterpret_cast<const f16x8*>(wp + s * 2048 + 1024);
             am = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, bh[s], am, 0, 0, 0);
             if (mt == 0 && s + 1 < UP_KSTEPS) convert(s + 1);       // the split of the next chunk issues under this chunk's MFMAs
             ac = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, bl[s], ac, 0, 0, 0);
@@ -126,9 +104,8 @@ __global__ __launch_bounds__(256, 2) void conv_up16_kernel(ConvArgs a, UpArgs u)
 #pragma unroll
         for (int qd = 0; qd < 4; ++qd) {
             const int ml = mt * 32 + 8 * qd + 4 * lh;       // GEMM row = phase * cout_real + co   (cout_g == 32 * MT)
-            float4 v = make_float4(fmaf(ac[4 * qd], kUpLoInv, am[4 * qd]), fmaf(ac[4 * qd + 1], kUpLoInv, am[4 * qd + 1]),
-                                   fmaf(ac[4 * qd + 2], kUpLoInv, am[4 * qd + 2]), fmaf(ac[4 * qd + 3], kUpLoInv, am[4 * qd + 3]));
-            bad |= !(fabsf(v.x) <= 3.0e38f) | !(fabsf(v.y) <= 3.0e38f) | !(fabsf(v.z) <= 3.0e38f) | !(fabsf(v.w) <= 3.0e38f);
+            float4 v = join4(am, ac, qd);
+            bad |= not_finite4(v);
             const float4 bb = *reinterpret_cast<const float4*>(blds + ml);
             v.x += bb.x; v.y += bb.y; v.z += bb.z; v.w += bb.w;
             const int ph = (int)(((float)ml + 0.5f) * u.inv_cout_real);        // ml / cout_real, exact for these sizes
@@ -147,8 +124,7 @@ bool conv_up16_supported(const ConvArgs& a) {
     if (a.act_out != ADK_ACT_NONE) return false;
     if (a.cin_g != UP_CIN || a.cout_g % 32 != 0 || a.cout_g > 96 || a.cout_real % 4 != 0) return false;
     if ((a.in_ch % 4) || (a.in_choff % 4) || (a.out_ch % 4) || (a.out_choff % 4)) return false;
-    if ((reinterpret_cast<uintptr_t>(a.in) | reinterpret_cast<uintptr_t>(a.out) | reinterpret_cast<uintptr_t>(a.wfrag)) & 15) return false;
-    if (a.bias && (reinterpret_cast<uintptr_t>(a.bias) & 15)) return false;
+    if (!aligned16(a.in) || !aligned16(a.out) || !aligned16(a.wfrag) || (a.bias && !aligned16(a.bias))) return false;
     return true;
 }
 
@@ -167,16 +143,12 @@ int launch_conv_up16(const ConvArgs& a, hipStream_t s) {
         ADK_HIP_CHECK(hipGetLastError());
         return ADK_OK;
     };
-    auto by_mt = [&](auto act) -> int {
+    return with_act_in(a.act_in, "conv: unsupported input activation for the up-sampling kernel", [&](auto act) -> int {
         constexpr int ACT = decltype(act)::value;
         if (u.m_tiles == 1) return go(conv_up16_kernel<ACT, 1>);
         if (u.m_tiles == 2) return go(conv_up16_kernel<ACT, 2>);
         return go(conv_up16_kernel<ACT, 3>);
-    };
-    if (a.act_in == ADK_ACT_ELU) return by_mt(std::integral_constant<int, ADK_ACT_ELU>());
-    if (a.act_in == ADK_ACT_LEAKY) return by_mt(std::integral_constant<int, ADK_ACT_LEAKY>());
-    if (a.act_in == ADK_ACT_NONE) return by_mt(std::integral_constant<int, ADK_ACT_NONE>());
-    return fail(ADK_ERR_ARG, "conv: unsupported input activation for the up-sampling kernel");
+    });
 }
 
 }  // namespace adk
