@@ -2,7 +2,7 @@
 // disc_gemm_grad_kernel, univ_disc.hip's conv2d_gemm_kernel and conv2d_gemm_grad_kernel), and what else the two families share:
 // the argument structs' pointers, the activation and its mask, the phase split of a strided backward, and the check of act / impl.
 //   Y[m][n] = bias[m] + sum_kk W[kk][m] X[kk][n]   on v_mfma_f32_32x32x2_f32 (f32 in, f32 accumulate: a k-ordered fmaf chain,
-//   no split precision), then LeakyReLU.
+//   no split precision), then LeakyReLU -- or another last step, the Epi parameter (dec_grad.hip's residual add and a'(x) factor).
 // Workgroup tile BM x BN x 16 of 4 waves, WM x WN waves each holding TM x TN tiles of 32 x 32.  The 16-deep K slice of W
 // (pre-transposed at load to [kk][m], coalesced along m) and of the implicit X are staged in LDS; the next slice is loaded into
 // registers while the current one is multiplied.  A thread stages one fixed column of X over the whole K loop.
@@ -70,8 +70,14 @@ static inline int cg_check_act_impl(const std::string& f, int act, float slope, 
     return ADK_OK;
 }
 
-template <int WM, int WN, int TM, int TN, class Src>
-__device__ __forceinline__ void conv_gemm_f32(Src& src, const float* __restrict__ bias, int act, float slope) {
+// The epilogue's last step: what is stored at dst for an accumulator with its bias added.  The discriminators' is the
+// activation; dec_grad.hip's add a residual or multiply by a saved input's activation derivative (Epi of conv_gemm_f32).
+struct CgActStore {
+    __device__ __forceinline__ void operator()(float* dst, float v, int act, float slope) const { *dst = cg_act(v, act, slope); }
+};
+
+template <int WM, int WN, int TM, int TN, class Src, class Epi = CgActStore>
+__device__ __forceinline__ void conv_gemm_f32(Src& src, const float* __restrict__ bias, int act, float slope, const Epi epi = Epi()) {
     static_assert(WM * WN * 64 == CG_THREADS, "four waves");
     constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
     static_assert(CG_THREADS % BN == 0 && (BM * CG_KT) % CG_THREADS == 0, "tile shape");
@@ -158,7 +164,7 @@ __device__ __forceinline__ void conv_gemm_f32(Src& src, const float* __restrict_
                 const int m = m0 + wm * TM * 32 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
                 if (m < mg) {
                     const float bv = bias ? bias[src.bias_index(m)] : 0.f;
-                    yb[(long long)m * ldy] = cg_act(acc[a][b][r] + bv, act, slope);
+                    epi(yb + (long long)m * ldy, acc[a][b][r] + bv, act, slope);
                 }
             }
     }

@@ -105,6 +105,11 @@ SYMBOLS = {
                                   C.c_float, _i32, _vp]),
     "adk_spectrogram_grad_workspace_bytes": (C.c_int64, [_i32, _i32, _i32, _i32, _i32]),
     "adk_spectrogram_grad": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "adk_dec_conv": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float, _i32, _vp]),
+    "adk_dec_conv_grad": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float, _vp]),
+    "adk_dec_convtr": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float, _vp]),
+    "adk_dec_convtr_grad": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float, _vp]),
+    "adk_rvq_st_grad": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "adk_packed_weight_floats_split16": (C.c_int64, [_i32, _i32, _i32]),
     "adk_pack_weights_split16": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "adk_codes_frame_bytes": (C.c_int32, [_i32, _i32]),

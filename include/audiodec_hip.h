@@ -422,6 +422,52 @@ int adk_spectrogram_grad(const float* x, const float* g, int32_t n_signals, int3
                          int32_t hop, const float* window, int32_t win_length, void* workspace, float* grad_x, void* stream);
 
 /*
+ * The symmetric decoder as a frozen, differentiable function of its input (models/autoencoder/modules/decoder.py:25-138 in
+ * 'causal' mode): a non-streaming forward on [n_items][c][t] tensors, the reference's layout, that writes every layer's output,
+ * and the backward to the input with the weights held constant.  Exact f32 (the f32-input MFMA's k-ordered fmaf chain); every
+ * output element is written exactly once, with no atomics: bitwise reproducible.
+ * a is the INPUT activation: act 0 = none, 1 = ELU(alpha), a(x) = x > 0 ? x : alpha expm1(x) with the inference kernels' expm1
+ * (bitwise their ELU for alpha = 1); a'(x) = x > 0 ? 1 : alpha (expm1(x) + 1).
+ * adk_dec_conv: CausalConv1d.forward (layers/conv_layer.py:146-149), one group, optionally fused with a skip connection:
+ *   x [n_items][c_in][t] -> y [n_items][c_out][t]
+ *   y[b][o][u] = bias[o] + sum_{ci, j < kernel} W[o][ci][j] a(x[b][ci][u - (kernel-1-j) dilation]) + res[b][o][u]
+ *   terms with a negative index are zero; bias [c_out] and res (of y's shape) may be NULL.
+ *   impl 1 (direct): w is the reference's [c_out][c_in][kernel]; one thread per output, meant for c_out = 1 or 2.
+ *   impl 2 (gemm):   w is [c_in * kernel][c_out] (the reference's weight transposed).  Both sum in the order kk = ci kernel + j.
+ * adk_dec_conv_grad: its backward to x, given dy of y's shape:
+ *   dx[b][ci][u] = a'(x[b][ci][u]) sum_{o, j} W[o][ci][j] dy[b][o][u + (kernel-1-j) dilation] + dres[b][ci][u]
+ *   terms with an index >= t are zero; x (the forward's input) is read, and required, only when act == 1; dres (of x's shape:
+ *   the gradient that reaches x through a skip connection) may be NULL.  w is [(o, j) at o kernel + j][c_in].
+ * adk_dec_convtr: CausalConvTranspose1d.forward (layers/conv_layer.py:189-192) for kernel == 2 stride, the only form the
+ *   reference builds: replicate padding by one frame, ConvTranspose1d, crop of one stride at both ends:
+ *   x [n_items][c_in][t] -> y [n_items][c_out][t stride]
+ *   y[b][o][i stride + r] = bias[o] + sum_ci W[ci][o][r] a(x[b][ci][i]) + W[ci][o][stride + r] a(x[b][ci][max(i-1, 0)])
+ *   w is [r < stride][(ci, tap) at 2 ci + tap][c_out], tap 0 = W[ci][o][r], tap 1 = W[ci][o][stride + r]; bias may be NULL.
+ * adk_dec_convtr_grad: its backward to x, given dy of y's shape:
+ *   dx[b][ci][i] = a'(x[b][ci][i]) sum_{o, q < 2 stride} W[ci][o][q] ([i stride + q < t stride] dy[b][o][i stride + q]
+ *                                                                   + [i == 0 and q >= stride] dy[b][o][q - stride])
+ *   (the last term is the replicate padding's share).  w is [(o, q) at o 2 stride + q][c_in]; x as in adk_dec_conv_grad.
+ * adk_rvq_st_grad: the backward of Quantizer.forward in eval mode to z (layers/vq_module.py:83-84, 119-134: the residual of
+ *   stage s >= 1 is a constant to autograd, so only stage 0 passes dzq and only vqloss[0] reaches z):
+ *   dz[b][c][u] = dzq[b][c][u] + up_vq[0] 2 (z[b][c][u] - codebook[idx[b t + u]][c]) / (n_items t dim)
+ *   z, dzq, dz [n_items][dim][t]; codebook [size][dim], stage 0's codes; idx [n_items t] int64, stage 0's emitted indices;
+ *   dzq (the gradient of zq) and up_vq (the gradient of vqloss, [n_q] f32 read on the device) may be NULL (zero).  An index
+ *   outside [0, size) reads code 0 and raises bit 0 of adk_debug_flags().
+ * n_items == 0 is a no-op.  Every argument is checked before any HIP call (ADK_ERR_ARG).  No allocation, no synchronisation.
+ */
+int adk_dec_conv(const float* x, const float* w, const float* bias, const float* res, float* y, int32_t n_items, int32_t c_in,
+                 int32_t t, int32_t c_out, int32_t kernel, int32_t dilation, int32_t act, float alpha, int32_t impl, void* stream);
+int adk_dec_conv_grad(const float* dy, const float* x, const float* w, const float* dres, float* dx, int32_t n_items,
+                      int32_t c_in, int32_t t, int32_t c_out, int32_t kernel, int32_t dilation, int32_t act, float alpha,
+                      void* stream);
+int adk_dec_convtr(const float* x, const float* w, const float* bias, float* y, int32_t n_items, int32_t c_in, int32_t t,
+                   int32_t c_out, int32_t kernel, int32_t stride, int32_t act, float alpha, void* stream);
+int adk_dec_convtr_grad(const float* dy, const float* x, const float* w, float* dx, int32_t n_items, int32_t c_in, int32_t t,
+                        int32_t c_out, int32_t kernel, int32_t stride, int32_t act, float alpha, void* stream);
+int adk_rvq_st_grad(const float* dzq, const float* up_vq, const float* z, const float* codebook, const int64_t* idx, float* dz,
+                    int32_t n_items, int32_t dim, int32_t t, int32_t size, void* stream);
+
+/*
  * Multi-resolution STFT loss and waveform-shape loss, one resolution / one window length per call (losses/stft_loss.py:19-170,
  * losses/waveform_loss.py:15-75).  The STFT is adk_logmel's: torch.stft's defaults, the window [win_length] centred in n_fft,
  * 1 + n_samples/hop frames, n_fft/2 + 1 bins, mag = sqrt(max(re^2 + im^2, eps)) (a NaN stays NaN).
