@@ -45,10 +45,8 @@
 // 32 v_mfma_f32_32x32x2_f32; main + cross/2048 is formed when a segment ends.  See conv_rl16.hip for the
 // error analysis.
 #include "conv_split16.h"      // the split-f16 operand format (SPLIT variants), act_in, buf_load4, the vector typedefs
-#include <cstdlib>
 #include <cstring>
 #include <atomic>
-#include <mutex>
 
 #ifndef ADK_SK_SC1_READ
 #define ADK_SK_SC1_READ 1   // 1: partial tiles read with sc1 loads, no acquire fence; 0: plain loads behind an agent-scope acquire
@@ -282,6 +280,7 @@ __device__ __forceinline__ void sk_epilogue_lds(const ConvArgs& a, const f32x16 
 // puts twice the bytes in flight per iteration and halves the iteration count.
 // WGM * WGN = 8 (512 threads, one workgroup per CU -- still 8 waves per CU): the 128 x 128 tile of the split variant, half the
 // operand bytes per MFMA of the 64 x 64 tile at the same number of waves in flight.
+// (Built: KD = 1 and 4-wave workgroups only -- launch_cfg and kCfgs say why.)
 template <int WGM, int WGN, int NJ, int ACT, bool SPLIT, int KD>
 __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN == 4) ? 2 : 1) void conv_sk_kernel(ConvArgs a, SkArgs sk) {
     constexpr int NT = 64 * WGM * WGN;                // threads per workgroup
@@ -930,64 +929,62 @@ bool conv_mfma_supported(const ConvArgs& a) {
 // ------------------------------------------------------------------------------------------------
 namespace {
 struct Cfg { int wgm, wgn, nj; const char* name; };
-const Cfg kCfgs[7] = {{4, 1, 2, "conv_sk<128x64>"}, {4, 1, 4, "conv_sk<128x128>"}, {2, 2, 1, "conv_sk<64x64>"},
-                      {2, 2, 2, "conv_sk<64x128>"}, {1, 4, 1, "conv_sk<32x128>"}, {1, 4, 2, "conv_sk<32x256>"},
-                      {4, 2, 2, "conv_sk<128x128w8>"}};       // 6: 8 waves (512 threads), split variant only
-int g_forced_cfg = -2;     // -2: not initialised (read ADK_CONV_CFG), -1: heuristic
-int g_occ = -1;            // persistent workgroups per CU (ADK_CONV_OCC, default 2)
-int g_fixed_g = 0;         // persistent workgroups per launch when > 0 (ADK_CONV_G / adk_set_conv_workgroups), else 256 * g_occ
-int g_oversub = 0;         // ADK_CONV_OVERSUB
-int g_aligned = 1;         // tile-aligned stream-K ranges where the rule in launch_cfg applies (ADK_CONV_ALIGNED=0: never)
-int g_max_split = 5;       // most workgroups sharing one tile (ADK_CONV_MAX_SPLIT; 0 = no limit).  Measured (tools/run_r2s.sh):
-                           // 5 vs no limit at 256 streams: last strided conv 30.9 -> 18.3 us, first transposed conv 25.2 -> 18.9,
-                           // K10 strided 24.1 -> 19.3; at 1 stream the grouped K11 256-channel conv 28.3 -> 18.9, projector 19.9 -> 13.9
-int g_min_units = 2;       // minimum K chunks per workgroup (ADK_CONV_MIN_UNITS; 2 measured best at 256 streams)
+// tile configs by id (adk_set_conv_cfg, the names in profiles).  Ids 1, 3, 5, 6 (128x128, 64x128, 32x256, the 8-wave 128x128) lost on every
+// layer of the path at 256 streams (profiles/r1_streamk_cfg_sweep.md) and have no build any more.
+const Cfg kCfgs[5] = {{4, 1, 2, "conv_sk<128x64>"}, {}, {2, 2, 1, "conv_sk<64x64>"}, {}, {1, 4, 1, "conv_sk<32x128>"}};
+int g_forced_cfg = -1;            // adk_set_conv_cfg: -1 = heuristic
+constexpr int kOcc = 2;           // persistent workgroups per CU
+constexpr long long kSlots = 256LL * kOcc;   // ... so a launch takes at most this many: a surplus would only start when the first ones end
+constexpr int kMaxSplit = 5;      // most workgroups sharing one tile.  Measured (tools/run_r2s.sh):
+                                  // 5 vs no limit at 256 streams: last strided conv 30.9 -> 18.3 us, first transposed conv 25.2 -> 18.9,
+                                  // K10 strided 24.1 -> 19.3; at 1 stream the grouped K11 256-channel conv 28.3 -> 18.9, projector 19.9 -> 13.9
+constexpr int kMinUnits = 2;      // minimum K chunks per workgroup (2 measured best at 256 streams)
+constexpr int kOwnerShare = 45;   // percent of a tile's chunks its owner takes when two workgroups share it and a CU (see sk_plan)
 
 // How many persistent workgroups a launch over `tiles` tiles of sk.nchunks chunks takes (at most `cap`) and where their ranges
 // are cut: fills sk.split / tpw / tiles / owner_chunks / total, returns G.  Pure host logic (adk_streamk_plan exposes it to the
 // CPU tests).
 long long sk_plan(long long tiles, long long cap, SkArgs& sk) {
     sk.total = tiles * sk.nchunks;
-    // persistent workgroups: 256 CUs x occupancy, but never fewer than g_min_units chunks per workgroup
+    // persistent workgroups: 256 CUs x occupancy, but never fewer than kMinUnits chunks per workgroup
     // (each one pays a fixed prologue/epilogue, and every cut of a tile costs a partial round trip)
     long long G = cap;
-    const long long by_units = (sk.total + g_min_units - 1) / g_min_units;
+    const long long by_units = (sk.total + kMinUnits - 1) / kMinUnits;
     if (G > by_units) G = (by_units + 7) / 8 * 8;
-    // ... and never more than g_max_split workgroups on one tile: its owner adds the others' partial tiles one after the
+    // ... and never more than kMaxSplit workgroups on one tile: its owner adds the others' partial tiles one after the
     // other, which is what a launch over few tiles (few streams, or the deepest layers) otherwise spends its time on
-    if (g_max_split > 0 && G > tiles * g_max_split) G = (tiles * g_max_split + 7) / 8 * 8;
+    if (G > tiles * kMaxSplit) G = (tiles * kMaxSplit + 7) / 8 * 8;
     sk.split = 0; sk.tpw = 0; sk.tiles = (int)tiles; sk.owner_chunks = 0;
     // Tile-aligned ranges (measured, tools/run_r2z.sh at 256 streams: a range that straddles two tiles pays two partial round
     // trips -- 200-tile 1x1 / strided / transposed convs 20.7 -> 10.8 / 13.0 / 13.4 us with one whole tile per workgroup, the
     // grouped K11 256-channel conv 50.8 -> 44.3 us with exact halves).  Short K (<= 8 chunks): whole tiles, as many per
     // workgroup as it takes.  Long K: an even split when >= 2 workgroups per tile fit (one workgroup per CU first, then
     // ~6 chunks each); a long-K layer with more tiles than that keeps the balanced split above.
-    if (g_aligned && tiles < (1 << 20)) {
-        const int ms = g_max_split > 0 ? g_max_split : 5;
+    if (tiles < (1 << 20)) {
         if (tiles > cap) {
             if (sk.nchunks <= 8) { sk.tpw = (int)((tiles + cap - 1) / cap); G = (tiles + sk.tpw - 1) / sk.tpw; }
         } else {
-            long long sp = std::max<long long>(std::min<long long>(ms, 256 / tiles), std::min<long long>(ms, sk.nchunks / 6));
+            long long sp = std::max<long long>(std::min<long long>(kMaxSplit, 256 / tiles), std::min<long long>(kMaxSplit, sk.nchunks / 6));
             if (sp < 1) sp = 1;
-            while (sp > 1 && (tiles * sp > cap || sk.nchunks / sp < g_min_units)) --sp;
+            while (sp > 1 && (tiles * sp > cap || sk.nchunks / sp < kMinUnits)) --sp;
             if (sp > 1 || sk.nchunks < 12) { sk.split = (int)sp; G = tiles * sp; }
             // two workgroups per tile AND per CU: the owners run on the later-dispatched blocks (see the kernel), which get the
-            // smaller share of a CU -- give them the smaller share of the tile (ADK_CONV_OWNER_SHARE percent, default 45)
+            // smaller share of a CU -- give them the smaller share of the tile (kOwnerShare percent)
             sk.owner_chunks = sk.nchunks / 2;
-            if (sk.split == 2 && G >= 448) {             // (measured: grouped K11 256-channel conv, G = 480: 41.9 -> 39.5 us; G = 400 loses)
-                static int share = -1;
-                if (share < 0) { const char* e = getenv("ADK_CONV_OWNER_SHARE"); share = (e && atoi(e) >= 10 && atoi(e) <= 90) ? atoi(e) : 45; }
-                sk.owner_chunks = std::max(g_min_units, std::min(sk.nchunks - g_min_units, (sk.nchunks * share + 50) / 100));
-            }
+            if (sk.split == 2 && G >= 448)               // (measured: grouped K11 256-channel conv, G = 480: 41.9 -> 39.5 us; G = 400 loses)
+                sk.owner_chunks = std::max(kMinUnits, std::min(sk.nchunks - kMinUnits, (sk.nchunks * kOwnerShare + 50) / 100));
         }
     }
     return G;
 }
 
-template <int WGM, int WGN, int NJ, bool SPLIT, int KD = 1>
+template <int WGM, int WGN, int NJ, bool SPLIT>
 int launch_cfg(const ConvArgs& a, hipStream_t s, Workspace& ws) {
-    constexpr int BM = 32 * WGM, BN = 32 * NJ * WGN, NT = 64 * WGM * WGN;
+    // KD = 1: 128-deep chunks (KD = 2) ran single launches of the small layers 20-30 % faster (transposed convs 26.6 -> 18.8 us, single-stream
+    // latency 1.09 -> 1.03 ms), but 67.6 KB of LDS per workgroup kept concurrently running programs off the CU: 3-stream pipeline 196 k vs 204 k frames/s
+    constexpr int BM = 32 * WGM, BN = 32 * NJ * WGN, NT = 64 * WGM * WGN, KD = 1;
     constexpr int KCC = KC * KD;
+    static_assert(NT == 256, "kSlots counts 256-thread workgroups");
     constexpr size_t lds = 2ull * BN * (KCC + 4) * sizeof(float);
     SkArgs sk;
     sk.m_tiles = (a.cout_g + BM - 1) / BM;
@@ -1006,10 +1003,7 @@ int launch_cfg(const ConvArgs& a, hipStream_t s, Workspace& ws) {
     }
     const long long tiles = (long long)sk.m_tiles * sk.n_tiles * a.groups;
     sk.total = tiles * sk.nchunks;
-    const long long slots = NT == 256 ? 256LL * g_occ : 256LL;        // resident workgroups: 512-thread workgroups are alone on their CU
-    // ADK_CONV_OVERSUB percent (tuning): allow that many more workgroups than slots -- the surplus starts when the first ones end
-    const long long lim = NT == 256 ? slots + slots * g_oversub / 100 : slots;
-    const long long cap = ws.workgroups > 0 ? std::min<long long>(ws.workgroups, lim) : (g_fixed_g > 0 ? std::min<long long>(g_fixed_g, lim) : lim);
+    const long long cap = ws.workgroups > 0 ? std::min<long long>(ws.workgroups, kSlots) : kSlots;
     const long long G = sk_plan(tiles, cap, sk);
     sk.G = (int)G;
     const size_t part_bytes = (size_t)sk.G * NT * NJ * 16 * sizeof(float);
@@ -1020,14 +1014,10 @@ int launch_cfg(const ConvArgs& a, hipStream_t s, Workspace& ws) {
     sk.epoch = ++ws.epoch;
     if (sk.epoch == 0) sk.epoch = ++ws.epoch;
     sk.err = conv_err_word(a);
-    {
-        // finished tiles through LDS (coalesced 16-byte accesses along the channel axis) where the tile image fits a staging buffer
-        // (<= 64 rows) and 8-channel groups never straddle a row / a phase of a transposed conv; ADK_SK_EPI_LDS=0: the round-1..3 epilogue
-        static int epi = -1;
-        if (epi < 0) { const char* e = getenv("ADK_SK_EPI_LDS"); epi = e ? atoi(e) : 1; }
-        sk.epi_lds = (epi && WGM <= 2 && a.cout_g % 8 == 0 && a.cout_real % 8 == 0 && a.out_ch % 8 == 0 && a.out_choff % 8 == 0 &&
-                      (!a.res || (a.res_ch % 4 == 0 && a.res_choff % 4 == 0 && a.res_gstride % 4 == 0))) ? 1 : 0;
-    }
+    // finished tiles through LDS (coalesced 16-byte accesses along the channel axis) where the tile image fits a staging buffer
+    // (<= 64 rows) and 8-channel groups never straddle a row / a phase of a transposed conv
+    sk.epi_lds = (WGM <= 2 && a.cout_g % 8 == 0 && a.cout_real % 8 == 0 && a.out_ch % 8 == 0 && a.out_choff % 8 == 0 &&
+                  (!a.res || (a.res_ch % 4 == 0 && a.res_choff % 4 == 0 && a.res_gstride % 4 == 0))) ? 1 : 0;
     if (lds > 64 * 1024) {
         static bool attr_set_dev[kMaxDevices] = {};      // function attributes are per device
         bool& attr_set = attr_set_dev[current_device()];
@@ -1063,14 +1053,16 @@ int launch_cfg(const ConvArgs& a, hipStream_t s, Workspace& ws) {
 }
 }  // namespace
 
-void conv_mfma_force_cfg(int cfg) { g_forced_cfg = cfg; }
+bool conv_mfma_force_cfg(int cfg) {
+    if (cfg != -1 && cfg != 0 && cfg != 2 && cfg != 4) return false;
+    g_forced_cfg = cfg;
+    return true;
+}
 
 int streamk_plan(long long tiles, int nchunks, int cap, int out[4]) {
-    (void)conv_mfma_workspace_bytes(nullptr);                      // reads the env knobs
     SkArgs sk{};
     sk.nchunks = nchunks;
-    const long long slots = 256LL * g_occ;
-    const long long G = sk_plan(tiles, cap > 0 ? std::min<long long>(cap, slots) : slots, sk);
+    const long long G = sk_plan(tiles, cap > 0 ? std::min<long long>(cap, kSlots) : kSlots, sk);
     out[0] = (int)G; out[1] = sk.split; out[2] = sk.tpw; out[3] = sk.owner_chunks;
     return ADK_OK;
 }
@@ -1093,26 +1085,17 @@ extern "C" int adk_debug_sk_trace(unsigned long long* out, int n) {      // debu
 
 // workspace = partial slots [G][256][NJ<=4][16] floats, then G publish flags
 size_t conv_mfma_workspace_bytes(size_t* flags_offset) {
-    if (g_occ < 0) {
-        const char* e = getenv("ADK_CONV_OCC"); g_occ = e ? atoi(e) : 2; if (g_occ < 1 || g_occ > 4) g_occ = 2;
-        e = getenv("ADK_CONV_MIN_UNITS"); if (e && atoi(e) >= 1) g_min_units = atoi(e);
-        e = getenv("ADK_CONV_MAX_SPLIT"); if (e && atoi(e) >= 0) g_max_split = atoi(e);
-        e = getenv("ADK_CONV_ALIGNED"); if (e) g_aligned = atoi(e) != 0;
-        e = getenv("ADK_CONV_OVERSUB"); if (e && atoi(e) >= 0 && atoi(e) <= 100) g_oversub = atoi(e);
-        e = getenv("ADK_CONV_G"); if (e && atoi(e) >= 8 && atoi(e) <= 2 * 256 * g_occ) g_fixed_g = atoi(e) / 8 * 8;
-    }
-    const size_t part = (size_t)256 * g_occ * 256 * 4 * 16 * sizeof(float);
+    const size_t part = (size_t)kSlots * 256 * 4 * 16 * sizeof(float);
     if (flags_offset) *flags_offset = part;
-    return part + (size_t)2 * 256 * g_occ * sizeof(unsigned)        // flags for up to twice the resident workgroups (oversubscribed plans)
+    return part + (size_t)kSlots * sizeof(unsigned)                 // one publish flag per workgroup
            + (size_t)kGvCounters * sizeof(unsigned);                // ... and the per-tile arrival counters of conv_gv16 (zero between launches)
 }
 
 int conv_mfma_pick(const ConvArgs& a) {
-    if (g_forced_cfg == -2) { const char* e = getenv("ADK_CONV_CFG"); g_forced_cfg = e ? atoi(e) : -1; }
-    if (g_forced_cfg >= 0 && g_forced_cfg <= 5) return g_forced_cfg;
+    if (g_forced_cfg == 2 || g_forced_cfg == 4) return g_forced_cfg;      // (a forced 0 is for the split-f16 kernel: f32 has no 128x64 build)
     // Measured over every layer of the path at 256 streams (profiles/r1_streamk_cfg_sweep.md): the
     // 32x32 wave tile wins everywhere -- 64x64 workgroup tiles when the group has >= 64 output
-    // channels, 32x128 otherwise.  (The wider tiles are kept for tuning via ADK_CONV_CFG.)
+    // channels, 32x128 otherwise.
     return (a.cout_g % 64 == 0) ? 2 : 4;
 }
 
@@ -1120,51 +1103,30 @@ const char* conv_mfma_cfg_name(int pick) { return kCfgs[pick].name; }
 
 int launch_conv_mfma(const ConvArgs& a, hipStream_t s, Workspace& ws) {
     if (a.n_total == 0) return ADK_OK;
-    (void)conv_mfma_workspace_bytes(nullptr);
-    switch (conv_mfma_pick(a)) {
-        case 0: return launch_cfg<4, 1, 2, false>(a, s, ws);
-        case 1: return launch_cfg<4, 1, 4, false>(a, s, ws);
-        case 2: return launch_cfg<2, 2, 1, false>(a, s, ws);
-        case 3: return launch_cfg<2, 2, 2, false>(a, s, ws);
-        case 4: return launch_cfg<1, 4, 1, false>(a, s, ws);
-        default: return launch_cfg<1, 4, 2, false>(a, s, ws);
-    }
+    return conv_mfma_pick(a) == 2 ? launch_cfg<2, 2, 1, false>(a, s, ws) : launch_cfg<1, 4, 1, false>(a, s, ws);
 }
 
 // split-f16 variant: wfrag = adk_pack_weights_split16 layout
 int conv_sk16_pick(const ConvArgs& a) {
-    if (g_forced_cfg == -2) { const char* e = getenv("ADK_CONV_CFG"); g_forced_cfg = e ? atoi(e) : -1; }
-    if (g_forced_cfg >= 0 && g_forced_cfg <= 6) return g_forced_cfg;
+    if (g_forced_cfg >= 0) return g_forced_cfg;
     // with the matrix-core time cut to 3/16 the weight / activation re-reads weigh more: 128-row tiles (each X chunk
     // staged once per 128 output channels) win when that still leaves >= 256 tiles (measured: grouped 128-channel
     // vocoder stage 47.7 vs 55.2 us; the 100-tile encoder block loses, 34.6 vs 28.2 us)
-    static int wide = -1;                             // ADK_SK16_WIDE=1 (tuning): 128-row tiles whenever the group has >= 128 channels
-    if (wide < 0) { const char* e = getenv("ADK_SK16_WIDE"); wide = e ? atoi(e) : 0; }
-    if (a.cout_g % 128 == 0 && (wide || (long long)(a.cout_g / 128) * ((a.n_total + 63) / 64) * a.groups >= 256)) return 0;
+    if (a.cout_g % 128 == 0 && (long long)(a.cout_g / 128) * ((a.n_total + 63) / 64) * a.groups >= 256) return 0;
     return (a.cout_g % 64 == 0) ? 2 : 4;
 }
 
 
 // ---- conv_gv16 host side ----
-// (atomics + one call_once env read, as for the RVQ options: adk_set_option may be called from another host thread than the one launching)
-static std::atomic<int> g_gv{1};         // ADK_GV16: 1 (default) = convs of few columns run as conv_gv16, 0 = never (the stream-K kernel takes them)
-static std::atomic<int> g_gv_maxn{32};   // ... "few" = at most this many columns (ADK_GV16_MAXN / option "gv16_max_columns"; default 32 = one n-tile)
-static std::once_flag g_gv_once;
-static void gv_read_env() {
-    std::call_once(g_gv_once, [] {
-        const char* e = getenv("ADK_GV16"); if (e) g_gv.store(atoi(e));
-        e = getenv("ADK_GV16_MAXN"); if (e) g_gv_maxn.store(atoi(e) < 0 ? 0 : atoi(e));
-    });
-}
+// (an atomic, as the RVQ options: adk_set_option may be called from another host thread than the one launching)
+static std::atomic<int> g_gv_maxn{32};   // convs of at most this many columns run as conv_gv16 (option "gv16_max_columns"; default 32 = one n-tile, 0 = never)
 int conv_set_option(const char* name, int value) {
     if (strcmp(name, "gv16_max_columns")) return 1;
-    gv_read_env();
     g_gv_maxn.store(value < 0 ? 0 : value);
     return 0;
 }
 bool conv_gv16_preferred(const ConvArgs& a) {
-    gv_read_env();
-    if (!g_gv.load() || !conv_mfma_supported(a) || a.n_total < 1 || a.n_total > g_gv_maxn.load() || a.ktot % 16) return false;
+    if (!conv_mfma_supported(a) || a.n_total < 1 || a.n_total > g_gv_maxn.load() || a.ktot % 16) return false;
     const long long steps = a.ktot / 16;
     const long long otiles = (long long)a.groups * ((a.cout_g + 31) / 32) * ((a.n_total + 31) / 32);
     if (steps > 15 * 24 || otiles > kGvCounters) return false;                // at most 15 slices of at most 24 steps
@@ -1211,26 +1173,11 @@ int launch_conv_gv16(const ConvArgs& a, hipStream_t s, Workspace& ws) {
 
 int launch_conv_sk16(const ConvArgs& a, hipStream_t s, Workspace& ws) {
     if (a.n_total == 0) return ADK_OK;
-    (void)conv_mfma_workspace_bytes(nullptr);
     if (conv_gv16_preferred(a)) return launch_conv_gv16(a, s, ws);
-    // ADK_SK16_KD=2: 128-deep chunks.  Measured: single launches of the small layers 20-30 % faster (transposed convs
-    // 26.6 -> 18.8 us), single-stream latency 1.09 -> 1.03 ms, but 67.6 KB of LDS per workgroup keeps concurrently
-    // running programs off the CU: 3-stream pipeline 196 k vs 204 k frames/s.  Default 64-deep.
-    static int kd = -1;
-    if (kd < 0) { const char* e = getenv("ADK_SK16_KD"); kd = (e && atoi(e) == 2) ? 2 : 1; }
-    const int pick = conv_sk16_pick(a);
-    if (kd == 2 && a.ktot > 64) {
-        // only the 64x64 tile fits 128-deep chunks without spilling (247 VGPRs; the wider tiles need > 256)
-        if (pick == 2) return launch_cfg<2, 2, 1, true, 2>(a, s, ws);
-    }
-    switch (pick) {
+    switch (conv_sk16_pick(a)) {
         case 0: return launch_cfg<4, 1, 2, true>(a, s, ws);
-        case 1: return launch_cfg<4, 1, 4, true>(a, s, ws);
         case 2: return launch_cfg<2, 2, 1, true>(a, s, ws);
-        case 3: return launch_cfg<2, 2, 2, true>(a, s, ws);
-        case 4: return launch_cfg<1, 4, 1, true>(a, s, ws);
-        case 6: return launch_cfg<4, 2, 2, true>(a, s, ws);
-        default: return launch_cfg<1, 4, 2, true>(a, s, ws);
+        default: return launch_cfg<1, 4, 1, true>(a, s, ws);
     }
 }
 

@@ -29,7 +29,6 @@
 // Per output element the operations and their order are exactly those of conv_rl16 (k ascending, acc0 + acc1/2048, + bias,
 // + residual): the result is BIT-IDENTICAL to the per-op path (tests/test_gpu_b256.py::test_residual_chains_are_bit_identical).
 #include "conv_split16.h"      // the operand format, act_split / join4 / not_finite4, ADK_LDS_DMA16, wait_vm
-#include <cstdlib>
 
 #ifndef ADK_RB16_PF32
 #define ADK_RB16_PF32 2            // weight prefetch distance in 16-k steps of the variants in use (tuning builds: -DADK_RB16_PF32=... etc.)
@@ -45,9 +44,6 @@
 #endif
 #ifndef ADK_RB16_ASYNC_TOUCH
 #define ADK_RB16_ASYNC_TOUCH 1     // 0: the L2 warm-up touches as volatile loads (each one waited for), as measured in profiles/r3_rb16_timeline.md sections 1-3
-#endif
-#ifndef ADK_RB16_RING_SLOTS32
-#define ADK_RB16_RING_SLOTS32 4    // LDS weight ring of the 32-channel chains: slots of 4 KiB = one group of two 16-k steps (round 4; see rb_mfma_ring)
 #endif
 #ifndef ADK_RB16_HIST_LATE
 #define ADK_RB16_HIST_LATE 1
@@ -679,14 +675,8 @@ __global__ __launch_bounds__(256, WPS) void conv_rb16_kernel(RbArgs r) {
 
 struct RbPlan { int C, ta, tb, ntw, spw, n_tiles, hm, rps, wr; size_t lds; long long blocks; };
 
-int rb_knob(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-
 int rb_streams_per_wg(int C, int batch, int t, int groups) {
-    static const int env128 = rb_knob("ADK_RB16_SPW", 0);        // tuning: streams per workgroup of the 128-channel chains
-    static const int env64 = rb_knob("ADK_RB16_SPW64", 0);       // ... of the 64-channel chains
     int s = (C == 128) ? 2 : 1;
-    if (env128 > 0 && C == 128) s = env128;
-    if (env64 > 0 && C == 64) s = env64;
     const int wm = 4 / (C / 32);                                  // waves per m-tile, up to 4 n-tiles each
     const int max_ntw = C == 128 ? 2 : 4;                         // n-tiles per wave the instantiations go up to
     while (s > 1 && (s > batch || (s * t + 31) / 32 > max_ntw * wm)) --s;
@@ -694,8 +684,7 @@ int rb_streams_per_wg(int C, int batch, int t, int groups) {
     // time is its MFMA loops over TWO 32-column tiles -- of which one stream of a 25-step frame fills 25 columns.  One stream per workgroup and ONE
     // tile per wave (NTW = 1) halve the loops (single stream: 9.6 -> ~5 us per conv of the vocoder's second stage, profiles/r5_rb16_trace_single_stream.log)
     // at twice the workgroups.  Larger launches keep two streams per workgroup: there the chip is full and a weight fragment should feed two tiles.
-    static const int few = rb_knob("ADK_RB16_FEW128", 128);
-    if (C == 128 && s == 2 && env128 <= 0 && (long long)batch * groups <= few && t <= 32) s = 1;
+    if (C == 128 && s == 2 && (long long)batch * groups <= 128 && t <= 32) s = 1;
     return s;
 }
 
@@ -705,16 +694,14 @@ int rb_streams_per_wg(int C, int batch, int t, int groups) {
 // a vmcnt(0) round trip), and a fragment crosses L2 -> CU once per workgroup instead of twice (64 channels) / four times (32).
 // Measured, 256 streams (profiles/r4_ring_ab.md): vocoder stage 2 (64 ch) 176 -> 166 us, encoder block 1 64.7 -> 61.8 us, pipeline +1.5 %.
 // Off for the three-tile 32-channel variant (two workgroups per CU, no spills to begin with): there the per-group barrier costs more
-// than the weight stream did (vocoder stage 3 139 -> 148 us) -- ADK_RB16_RING=2 switches it on for A/B, =0 switches all rings off.
+// than the weight stream did (vocoder stage 3 139 -> 148 us).
 // 128 channels: every wave has an m-tile of its own, nothing to share.
 // Round 5: not for launches of <= 128 workgroups (few streams: at most one workgroup on half of the CUs) -- the ring's hand-over per group (a counted
 // wait + a barrier every one or two 16-k steps) costs a lone workgroup more than the second weight stream did: 1 / 32 streams 0.715 / 0.761 ms per
 // step with the ring, 0.707 / 0.752 without (experiments/sessions/r5_s12.sh).
 int rb_ring_slots(int C, int ntw, int spw, long long blocks) {
-    static const int on = rb_knob("ADK_RB16_RING", 1);
-    if (!on || (blocks <= 128 && on < 3)) return 0;
+    if (blocks <= 128) return 0;
     if (C == 32 && ntw == 2) return 3;
-    if (C == 32 && ntw == 3 && on >= 2) return ADK_RB16_RING_SLOTS32;
     if (C == 64 && ntw == 2 && spw == 1) return 3;        // three 4 KiB slots is what three workgroups per CU leave room for
     return 0;
 }
@@ -841,22 +828,19 @@ int launch_conv_rb16(const ConvArgs* c, int n, const int* keep, hipStream_t s) {
     // weight ring: vocoder stage 2 (768 workgroups) stage-in 16.7 us, chain 168 -> 152 us without the touches, stage 3 139 -> 137.
     // The 128-channel chains would spend 22 line touches per lane and conv on it (17 us of prologue, no gain in the loops:
     // profiles/r3_rb16_timeline.md) -- their waves walk the weights in lockstep instead (LS).
-    // ADK_RB16_WARM: 0 never, 1 always, 2 = the round-3 rule (32 / 64 channels, any launch size).
-    static const int warm_env = rb_knob("ADK_RB16_WARM", -1);
     // Round 5: not for launches of <= 128 workgroups either (few streams) -- there the touches cost more than they save: 1 / 8 / 32 streams
     // 0.719 / 0.750 / 0.772 ms per step with them, 0.713 / 0.746 / 0.761 without (experiments/sessions/r5_s11.sh); with them on the 128-channel chains too: 0.760 / 0.824 / 0.818.
-    r.warm = warm_env == 2 ? (pl.C <= 64) : (warm_env >= 0 ? warm_env : (pl.C <= 64 && pl.blocks <= 384 && pl.blocks > 128));
+    r.warm = pl.C <= 64 && pl.blocks <= 384 && pl.blocks > 128;
 #if ADK_RB16_DBG & 1
     r.dbg_slot = g_rb_launch++;
 #endif
     {
         // helper workgroups (see the kernel head): launches of at most kHelperBlocks computing workgroups; per XCD the weights of the groups it hosts
-        // must fit its L2 beside everything else: the longest prefix of convs within kHelperBytes.  ADK_RB16_HELPERS: helpers per XCD (0 = off).
-        static const int per_xcd = rb_knob("ADK_RB16_HELPERS", 4);
-        static const int max_blocks = rb_knob("ADK_RB16_HELPER_BLOCKS", 64);
+        // must fit its L2 beside everything else: the longest prefix of convs within kHelperBytes.
+        constexpr int kHelpersPerXcd = 4, kHelperBlocks = 64;
         constexpr long long kHelperBytes = 3584 * 1024;
         r.n_main = (int)pl.blocks; r.helpers = 0; r.helper_convs = 0;
-        if (per_xcd > 0 && pl.blocks <= max_blocks && a0.groups <= 32) {
+        if (pl.blocks <= kHelperBlocks && a0.groups <= 32) {
             int worst = 0;                                   // most distinct groups on one XCD
             for (int x = 0; x < 8; ++x) {
                 unsigned seen = 0; int cnt = 0;
@@ -870,7 +854,7 @@ int launch_conv_rb16(const ConvArgs* c, int n, const int* keep, hipStream_t s) {
                 if (bytes + one > kHelperBytes) break;
                 bytes += one;
             }
-            if (kc > 0 && worst > 0) { r.helpers = per_xcd; r.helper_convs = kc; }
+            if (kc > 0 && worst > 0) { r.helpers = kHelpersPerXcd; r.helper_convs = kc; }
         }
     }
     const int act = a0.act_in;
@@ -882,11 +866,7 @@ int launch_conv_rb16(const ConvArgs* c, int n, const int* keep, hipStream_t s) {
     // profiles/r3_rb16_timeline.md.  Now 4 waves x (3, 3, 2, 2) tiles, the odd tiles rotating with the workgroup.)
     // Round 4: with the shared LDS weight ring (pl.wr slots, rb_mfma_ring) no weight fragment lives in registers -- the PF argument is
     // then unused (1) -- and the 168-register variants have room for the residual again.
-    if (pl.C == 32 && pl.wr > 0) {
-        if (pl.ntw == 2) return rb_by_taps<32, 2, 1, 3, 1, true, 0, 3>(r, pl, act, s);
-        if (pl.ta == 11) return rb_by_taps<32, 3, 1, 2, 1, false, 0, ADK_RB16_RING_SLOTS32>(r, pl, act, s);
-        return rb_by_taps<32, 3, 1, 2, 1, true, 0, ADK_RB16_RING_SLOTS32>(r, pl, act, s);
-    }
+    if (pl.C == 32 && pl.wr > 0) return rb_by_taps<32, 2, 1, 3, 1, true, 0, 3>(r, pl, act, s);        // (rb_ring_slots: two tiles per wave only)
     if (pl.C == 64 && pl.wr > 0) return rb_by_taps<64, 2, 1, 3, 1, ADK_RB16_EARLY64, 0, 3>(r, pl, act, s);
     // (launches of <= 128 workgroups, round 5: no ring -- and no reason to squeeze the two-tile variants into 168 registers for a third workgroup per CU
     // that never comes: the 256-register builds of the same code have no spills, the 168-register ones 30-33 spilled registers without the ring)

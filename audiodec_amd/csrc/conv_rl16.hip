@@ -4,7 +4,6 @@
 // operand carried as two f16 numbers and three v_mfma_f32_32x32x16_f16 per 16 k: the format, its error and its overflow
 // check are described in conv_split16.h.
 #include "conv_split16.h"
-#include <cstdlib>
 
 #ifndef ADK_RL16_DBG
 #define ADK_RL16_DBG 0      // tuning experiments only: 1 = reuse the first weight fragment, 2 = no epilogue stores, 4 = no MFMA, 8 = no staging loads, 16 = per-workgroup wall clocks
@@ -403,12 +402,6 @@ bool conv_rl16_supported(const ConvArgs& a) {
     return conv_io_aligned(a);
 }
 
-static bool rl16_few_streams() {                 // ADK_RL16_FEW=0 (tuning): the round-1 rule -- rows kernel only when >= 192 long tiles
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("ADK_RL16_FEW"); v = e ? atoi(e) : 1; }
-    return v != 0;
-}
-
 // Time steps per workgroup.  0: the history does not fit.
 static int rl16_time_tile(const ConvArgs& a) {
     const int rs = 4 * a.cin_g + 16;
@@ -420,7 +413,7 @@ static int rl16_time_tile(const ConvArgs& a) {
     // few streams: one n-tile per workgroup while that keeps the launch within one round of resident workgroups (3 per CU).
     // Re-staging the history per tile costs nothing when most CUs would idle otherwise (measured, tools/run_r2q.sh: the
     // 32-channel K7 conv at 1 / 32 / 64 streams 9.9 / 10.5 / 10.7 -> 6.4 / 7.1 / 8.5 us; stream-K takes 15 / 17 / 20 us)
-    if (rl16_few_streams() && nt32 > 1 && (long long)a.batch * nt32 * a.groups <= 768) tt = 32;
+    if (nt32 > 1 && (long long)a.batch * nt32 * a.groups <= 768) tt = 32;
     // one tile would cover the whole call: cut a long one (>= 8 n-tiles, e.g. the 300-step frame of the 32-channel
     // layers) into two balanced halves -- twice the workgroups, two dispatch rounds whose load / matrix-core / store
     // phases overlap instead of running in lockstep (measured 38.0 -> 34.2 us; shorter tiles lose to the re-staged history)
@@ -429,9 +422,6 @@ static int rl16_time_tile(const ConvArgs& a) {
     // conv: 3 m-tiles x 2 pairs) when halving it leaves at most one item per wave
     else if (tt >= a.t_out && nt32 >= 4 && (a.cout_g / 32) * ((nt32 + 1) / 2) > 4 && (a.cout_g / 32) * (((nt32 + 1) / 2 + 1) / 2) <= 4)
         tt = ((nt32 + 1) / 2) * 32;
-    static int tt_env = -1;                                                  // tuning: shorter time tiles (more, smaller workgroups)
-    if (tt_env < 0) { const char* e = getenv("ADK_RL16_TT"); tt_env = e ? atoi(e) : 0; }
-    if (tt_env >= 32 && tt_env < tt) tt = tt_env / 32 * 32;
     return tt;
 }
 
@@ -439,10 +429,7 @@ static int rl16_time_tile(const ConvArgs& a) {
 // stream (measured faster than the stream-K variant at every stream count from 1 to 256, tools/run_r2q.sh)
 bool conv_rl16_preferred(const ConvArgs& a) {
     if (!conv_rl16_supported(a) || a.t_out < 24) return false;
-    const int tt = rl16_time_tile(a);
-    if (tt <= 0) return false;
-    if (!rl16_few_streams()) return (long long)a.batch * ((a.t_out + tt - 1) / tt) * a.groups >= 192;
-    return true;
+    return rl16_time_tile(a) > 0;
 }
 
 namespace {

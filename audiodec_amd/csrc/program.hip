@@ -72,36 +72,25 @@ static int ensure_workspace(Workspace& w) {
     return ADK_OK;
 }
 
-// run-time options: read once from the environment (read_env), set by adk_set_option from any host thread -- atomics, like the rvq and conv options
-static std::atomic<int> g_use_rl{-1};       // ADK_CONV_RL=0 disables the rows-in-LDS kernel in AUTO mode (tuning aid)
-static std::atomic<int> g_use_up{-1};       // ADK_CONV_UP16=0 disables the up-sampling streamer in AUTO mode (tuning aid)
-static std::atomic<int> g_use_chain{-1};    // ADK_CHAIN=0: residual chains run op by op (A/B against the per-op kernels)
-static std::atomic<int> g_chain_max_c{-1};  // adk_set_option("chain_max_channels") / ADK_CHAIN_MAXC
-static std::atomic<int> g_chain_min_c{-1};  // adk_set_option("chain_min_channels") / ADK_CHAIN_MINC
-static std::atomic<int> g_chain_min_blocks{-1};   // adk_set_option("chain_min_blocks") / ADK_CHAIN_MIN_BLOCKS: fewer (stream, group) workgroups -> per-op launches
-static std::atomic<int> g_use_ou{-1};       // adk_set_option("conv_ou16") / ADK_CONV_OU16=0: conv_out and the last up-sampler stay two launches (A/B, tests)
-static std::atomic<int> g_use_oc{-1};       // adk_set_option("conv_oc16") / ADK_CONV_OC16=0: the last conv_out and the output conv stay two launches
-static std::atomic<int> g_use_cw{-1};       // adk_set_option("conv_cin1w") / ADK_CONV_CIN1W=0: the encoder's ring write stays a launch of its own
+// run-time options, set by adk_set_option from any host thread -- atomics, like the rvq and conv options
+static std::atomic<int> g_use_chain{-1};    // ADK_CHAIN=0 (read once, chains_enabled): residual chains run op by op (A/B against the per-op kernels)
+static std::atomic<int> g_chain_max_c{128}; // adk_set_option("chain_max_channels"): chains of wider layers run op by op
+// chains of fewer (stream, group) workgroups run op by op.  0: none does -- the crossover round 3 measured at ~160 pairs (tools/chain_crossover.py,
+// profiles/r3_chain_crossover.log) went away with the round-4 chain kernels (profiles/r4_few_streams.md); tests use the option for the per-op reference
+static std::atomic<int> g_chain_min_blocks{0};    // adk_set_option("chain_min_blocks")
+static std::atomic<int> g_use_ou{1};        // adk_set_option("conv_ou16", 0): conv_out and the last up-sampler stay two launches (A/B, tests)
+static std::atomic<int> g_use_oc{1};        // adk_set_option("conv_oc16", 0): the last conv_out and the output conv stay two launches
+static std::atomic<int> g_use_cw{1};        // adk_set_option("conv_cin1w", 0): the encoder's ring write stays a launch of its own
 
 static bool is_split16(int impl) {
     return impl == ADK_IMPL_SPLIT16 || impl == ADK_IMPL_SPLIT16_ROWS || impl == ADK_IMPL_SPLIT16_SK || impl == ADK_IMPL_SPLIT16_UP;
 }
-static void read_env() {
-    if (g_use_rl < 0) { const char* e = getenv("ADK_CONV_RL"); g_use_rl = e ? atoi(e) : 1; }
-    if (g_use_up < 0) { const char* e = getenv("ADK_CONV_UP16"); g_use_up = e ? atoi(e) : 1; }
+static bool chains_enabled() {
     if (g_use_chain < 0) { const char* e = getenv("ADK_CHAIN"); g_use_chain = e ? atoi(e) : 1; }
-    if (g_chain_max_c < 0) { const char* e = getenv("ADK_CHAIN_MAXC"); g_chain_max_c = e ? atoi(e) : 128; }
-    if (g_chain_min_c < 0) { const char* e = getenv("ADK_CHAIN_MINC"); g_chain_min_c = e ? atoi(e) : 0; }
-    // measured crossover (tools/chain_crossover.py, profiles/r3_chain_crossover.log): below ~160 (stream, group) pairs the per-op launches,
-    // which spread one stream's time tiles over many CUs, are faster than one workgroup per pair walking the whole chain
-    if (g_chain_min_blocks < 0) { const char* e = getenv("ADK_CHAIN_MIN_BLOCKS"); g_chain_min_blocks = e ? atoi(e) : 0; }
-    if (g_use_ou < 0) { const char* e = getenv("ADK_CONV_OU16"); g_use_ou = e ? atoi(e) : 1; }
-    if (g_use_oc < 0) { const char* e = getenv("ADK_CONV_OC16"); g_use_oc = e ? atoi(e) : 1; }
-    if (g_use_cw < 0) { const char* e = getenv("ADK_CONV_CIN1W"); g_use_cw = e ? atoi(e) : 1; }
+    return g_use_chain != 0;
 }
 
 static int run_conv(const ConvArgs& a, int impl, hipStream_t s, Workspace& ws) {
-    read_env();
     const bool ok = conv_mfma_supported(a);
     if (impl == ADK_IMPL_MFMA_ROWS) {
         if (!conv_rl_supported(a)) return fail(ADK_ERR_SHAPE, "conv: rows-in-LDS kernel needs stride 1, 32/64 channels per group, w_frag");
@@ -114,11 +103,11 @@ static int run_conv(const ConvArgs& a, int impl, hipStream_t s, Workspace& ws) {
         // rows-in-LDS when it fills the chip, else stream-K
         if (impl == ADK_IMPL_SPLIT16_UP && !conv_up16_supported(a))
             return fail(ADK_ERR_SHAPE, "conv: the up-sampling streamer takes 2-tap transposed convs with 64 input channels and <= 96 GEMM rows");
-        if (impl == ADK_IMPL_SPLIT16_UP || (impl == ADK_IMPL_SPLIT16 && g_use_up && conv_up16_supported(a)))
+        if (impl == ADK_IMPL_SPLIT16_UP || (impl == ADK_IMPL_SPLIT16 && conv_up16_supported(a)))
             return launch_conv_up16(a, s);
         if (impl == ADK_IMPL_SPLIT16_ROWS && !conv_rl16_supported(a))
             return fail(ADK_ERR_SHAPE, "conv: split-f16 rows-in-LDS kernel needs stride 1, 32/64 channels per group, K in {3,7,11}, split16 w_frag");
-        if (impl == ADK_IMPL_SPLIT16_ROWS || (impl == ADK_IMPL_SPLIT16 && g_use_rl && conv_rl16_preferred(a)))
+        if (impl == ADK_IMPL_SPLIT16_ROWS || (impl == ADK_IMPL_SPLIT16 && conv_rl16_preferred(a)))
             return launch_conv_rl16(a, s);
         if (!ok) return fail(ADK_ERR_SHAPE, "conv: split-f16 kernel needs w_frag, cin_g % 32 == 0 and 16-byte aligned rows");
         int rc = ensure_workspace(ws);
@@ -129,7 +118,7 @@ static int run_conv(const ConvArgs& a, int impl, hipStream_t s, Workspace& ws) {
     if (impl == ADK_IMPL_MFMA && !ok)
         return fail(ADK_ERR_SHAPE, "conv: MFMA kernel needs w_frag, cin_g % 32 == 0 and 16-byte aligned rows");
     if (want_mfma) {
-        if (impl == ADK_IMPL_AUTO && g_use_rl && conv_rl_preferred(a)) return launch_conv_rl(a, s);
+        if (impl == ADK_IMPL_AUTO && conv_rl_preferred(a)) return launch_conv_rl(a, s);
         int rc = ensure_workspace(ws);
         if (rc != ADK_OK) return rc;
         return launch_conv_mfma(a, s, ws);
@@ -141,16 +130,15 @@ static int run_conv(const ConvArgs& a, int impl, hipStream_t s, Workspace& ws) {
 
 // name of the kernel run_conv would launch for these arguments (profiles, tests)
 static std::string conv_kernel_name(const ConvArgs& a, int impl) {
-    read_env();
     if (is_split16(impl)) {
-        if (impl == ADK_IMPL_SPLIT16_UP || (impl == ADK_IMPL_SPLIT16 && g_use_up && conv_up16_supported(a))) return "conv_up16<64>";
-        const bool rows = impl == ADK_IMPL_SPLIT16_ROWS || (impl == ADK_IMPL_SPLIT16 && g_use_rl && conv_rl16_preferred(a));
+        if (impl == ADK_IMPL_SPLIT16_UP || (impl == ADK_IMPL_SPLIT16 && conv_up16_supported(a))) return "conv_up16<64>";
+        const bool rows = impl == ADK_IMPL_SPLIT16_ROWS || (impl == ADK_IMPL_SPLIT16 && conv_rl16_preferred(a));
         if (rows) return a.cin_g == 32 ? "conv_rl16<32>" : "conv_rl16<64>";
         if (conv_gv16_preferred(a)) return "conv_gv16<32>";
         return std::string(conv_mfma_cfg_name(conv_sk16_pick(a))).replace(0, 7, "conv_sk16");
     }
     const bool mf = impl != ADK_IMPL_DIRECT && conv_mfma_supported(a) && (impl == ADK_IMPL_MFMA || impl == ADK_IMPL_MFMA_ROWS || a.groups * a.cout_g >= 32);
-    const bool rl = mf && ((impl == ADK_IMPL_MFMA_ROWS && conv_rl_supported(a)) || (impl == ADK_IMPL_AUTO && g_use_rl && conv_rl_preferred(a)));
+    const bool rl = mf && ((impl == ADK_IMPL_MFMA_ROWS && conv_rl_supported(a)) || (impl == ADK_IMPL_AUTO && conv_rl_preferred(a)));
     if (rl) return a.cin_g == 32 ? "conv_rl<32>" : "conv_rl<64>";
     if (mf) return conv_mfma_cfg_name(conv_mfma_pick(a));
     return a.groups * a.cout_g == 1 ? "conv_cout1" : (a.cin_g == 1 && a.taps == 7 ? "conv_cin1" : "conv_direct");
@@ -162,12 +150,13 @@ using namespace adk;
 
 extern "C" const char* adk_last_error(void) { return g_err.c_str(); }
 extern "C" int adk_abi_version(void) { return ADK_ABI_VERSION; }
-extern "C" int adk_set_conv_cfg(int32_t cfg) { conv_mfma_force_cfg(cfg); return ADK_OK; }
+extern "C" int adk_set_conv_cfg(int32_t cfg) {
+    if (!conv_mfma_force_cfg(cfg)) return fail(ADK_ERR_ARG, "adk_set_conv_cfg: the library has tile configs 0 (128x64, split-f16 only), 2 (64x64) and 4 (32x128); -1 = heuristic");
+    return ADK_OK;
+}
 extern "C" int adk_set_option(const char* name, int32_t value) {
     if (!name) return fail(ADK_ERR_ARG, "adk_set_option: null name");
-    read_env();
     if (!strcmp(name, "chain_max_channels")) { g_chain_max_c = value < 0 ? 0 : value; return ADK_OK; }
-    if (!strcmp(name, "chain_min_channels")) { g_chain_min_c = value < 0 ? 0 : value; return ADK_OK; }
     if (!strcmp(name, "chain_min_blocks")) { g_chain_min_blocks = value < 0 ? 0 : value; return ADK_OK; }
     if (!strcmp(name, "conv_ou16")) { g_use_ou = value != 0; return ADK_OK; }
     if (!strcmp(name, "conv_oc16")) { g_use_oc = value != 0; return ADK_OK; }
@@ -471,7 +460,6 @@ static int op_conv_args(adk_program* p, int i, int frames, void* const* ext, Con
 // 2: the 1x1 conv_out of a vocoder stage + the next stage's activation and transposed conv (conv_ou16);
 // 3: the last 1x1 conv_out + activation + the output conv and its activation (conv_oc16)
 static int op_pair_kind(adk_program* p, int i, int frames, void* const* ext, ConvArgs& a1, ConvArgs& a2) {
-    read_env();
     if (i + 1 >= (int)p->ops.size()) return 0;
     const adk_op_desc &o1 = p->ops[i], &o2 = p->ops[i + 1];
     if (o1.kind != ADK_OP_CONV || o2.kind != ADK_OP_CONV || !o1.fuse_next || o1.impl != ADK_IMPL_SPLIT16) return 0;
@@ -481,8 +469,8 @@ static int op_pair_kind(adk_program* p, int i, int frames, void* const* ext, Con
     if (o2.impl == ADK_IMPL_AUTO && o2.conv.groups * o2.conv.cout_g == 1)      // (a one-channel conv has no matrix-core form: exact f32 in either arithmetic)
         return g_use_oc && conv_oc16_fusable(a1, a2) ? 3 : 0;
     if (o2.impl != ADK_IMPL_SPLIT16) return 0;
-    if (g_use_rl && conv_rl16_fusable(a1, a2)) return 1;
-    if (g_use_ou && g_use_up && conv_ou16_fusable(a1, a2)) return 2;
+    if (conv_rl16_fusable(a1, a2)) return 1;
+    if (g_use_ou && conv_ou16_fusable(a1, a2)) return 2;
     return 0;
 }
 static bool op_pair_fusable(adk_program* p, int i, int frames, void* const* ext, ConvArgs& a1, ConvArgs& a2) {
@@ -492,10 +480,9 @@ static bool op_pair_fusable(adk_program* p, int i, int frames, void* const* ext,
 // Can ops [i, i + n) (a residual chain, adk_op_desc.chain) run as one launch for a `frames`-hop step?  Fills c[] / keep[].
 constexpr int kMaxChain = 8;
 static bool op_chain_fusable(adk_program* p, int i, int frames, void* const* ext, ConvArgs* c, int* keep) {
-    read_env();
     const int n = p->ops[i].chain;
-    if (!g_use_chain || !g_use_rl || n < 2 || n > kMaxChain || i + n > (int)p->ops.size()) return false;
-    if (p->ops[i].conv.cin_g > g_chain_max_c || p->ops[i].conv.cin_g < g_chain_min_c) return false;
+    if (!chains_enabled() || n < 2 || n > kMaxChain || i + n > (int)p->ops.size()) return false;
+    if (p->ops[i].conv.cin_g > g_chain_max_c) return false;
     if ((long long)p->batch * p->ops[i].conv.groups < g_chain_min_blocks) return false;
     for (int k = 0; k < n; ++k) {
         const adk_op_desc& o = p->ops[i + k];
@@ -510,7 +497,6 @@ static bool op_chain_fusable(adk_program* p, int i, int frames, void* const* ext
 
 // Op i writes the caller's rows into a one-channel ring and op i + 1 is the Cin = 1 conv that reads it: one launch (conv_cin1w_kernel)?
 static bool op_write_conv_fusable(adk_program* p, int i, int frames, void* const* ext, ConvArgs& a) {
-    read_env();
     if (!g_use_cw || i + 1 >= (int)p->ops.size()) return false;
     const adk_op_desc &o1 = p->ops[i], &o2 = p->ops[i + 1];
     if (o1.kind != ADK_OP_RING_WRITE || o2.kind != ADK_OP_CONV || o1.mean_off >= 0 || o1.scale_off >= 0 || o2.in_ring != o1.out_ring) return false;

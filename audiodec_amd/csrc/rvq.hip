@@ -146,106 +146,6 @@ __global__ __launch_bounds__(RVQ_THREADS) void rvq_encode_kernel(const float* __
         }
 }
 
-// ---- v2: the same arithmetic, shorter dependency chain per stage (dim == 64, size == 1024) ----
-// One thread = one code, its 64 components live in REGISTERS for the stage:
-//   * all 64 component loads of a stage are in flight at once (v1: four dependent batches of 16), and the NEXT stage's are
-//     issued as soon as the winner has handed its code over -- they land during the residual update and two barriers;
-//   * the winning thread writes q from its registers to LDS (v1: a dependent gather from global memory after the argmax);
-//   * every thread folds the 16 per-wave candidates itself (v1: RB threads + a barrier), wave rr owns row rr: it keeps r and
-//     the running sum of q' in registers and forms |r|^2 for the next stage right after the update (v1: its own phase).
-// Three barriers per stage instead of five, ~3 us per stage instead of ~11.  Per element the operations and their order are
-// v1's (ascending-d fmaf chain, the same butterfly for |r|^2, the same (value, index) merges), so the indices are the same.
-template <int RB>
-__global__ __launch_bounds__(RVQ_THREADS) void rvq_encode_v2_kernel(const float* __restrict__ z, const float* __restrict__ embed,
-                                                                    const float* __restrict__ enorm, long long* __restrict__ idx,
-                                                                    float* __restrict__ zq, int n_rows, int n_q) {
-    constexpr int D = 64, SIZE = 1024;
-    __shared__ __attribute__((aligned(16))) float r2t_sh[D][RB];   // 2*r, dim-major: one broadcast read per d for all RB rows
-    __shared__ __attribute__((aligned(16))) float q_sh[RB][D];
-    __shared__ float rn_sh[RB];
-    __shared__ float red_v[RB][RVQ_WAVES];
-    __shared__ int red_i[RB][RVQ_WAVES];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int row0 = blockIdx.x * RB;
-    const bool owner = wave < RB;                          // wave rr owns row rr, lane = dimension
-    float r_reg = 0.f, qsum = 0.f;
-    float e[D];
-    auto load_codes = [&](int st) {
-        const float* Ec = embed + (size_t)st * D * SIZE + tid;
-#pragma unroll
-        for (int d = 0; d < D; ++d) e[d] = Ec[(size_t)d * SIZE];
-    };
-    load_codes(0);
-    if (owner) {
-        r_reg = (row0 + wave < n_rows) ? z[(size_t)(row0 + wave) * D + lane] : 0.f;
-        r2t_sh[lane][wave] = 2.f * r_reg;
-        float v = __fmul_rn(r_reg, r_reg);                 // flatten.pow(2).sum(1): the butterfly of v1
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) v = __fadd_rn(v, __shfl_xor(v, off, 64));
-        if (lane == 0) rn_sh[wave] = v;
-    }
-    __syncthreads();
-    for (int st = 0; st < n_q; ++st) {
-        float acc[RB];
-#pragma unroll
-        for (int rr = 0; rr < RB; ++rr) acc[rr] = 0.f;
-#pragma unroll
-        for (int d = 0; d < D; ++d) {                      // (2*flatten) @ embed, d ascending (vq_module.py:95)
-            if constexpr (RB == 4) {
-                const float4 r2 = *reinterpret_cast<const float4*>(&r2t_sh[d][0]);
-                acc[0] = fmaf(r2.x, e[d], acc[0]); acc[1] = fmaf(r2.y, e[d], acc[1]);
-                acc[2] = fmaf(r2.z, e[d], acc[2]); acc[3] = fmaf(r2.w, e[d], acc[3]);
-            } else if constexpr (RB == 2) {
-                const float2 r2 = *reinterpret_cast<const float2*>(&r2t_sh[d][0]);
-                acc[0] = fmaf(r2.x, e[d], acc[0]); acc[1] = fmaf(r2.y, e[d], acc[1]);
-            } else {
-#pragma unroll
-                for (int rr = 0; rr < RB; ++rr) acc[rr] = fmaf(r2t_sh[d][rr], e[d], acc[rr]);
-            }
-        }
-        const float en = enorm[(size_t)st * SIZE + tid];
-#pragma unroll
-        for (int rr = 0; rr < RB; ++rr) {                  // dist = (|r|^2 - 2rE) + |E|^2 ; argmax(-dist), lowest index on ties
-            float v = -__fadd_rn(__fsub_rn(rn_sh[rr], acc[rr]), en);
-            int i = tid;
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) {
-                const float v2 = __shfl_xor(v, off, 64);
-                const int i2 = __shfl_xor(i, off, 64);
-                argmax_merge(v, i, v2, i2);
-            }
-            if (lane == 0) { red_v[rr][wave] = v; red_i[rr][wave] = i; }
-        }
-        __syncthreads();                                   // A: candidates of all waves visible
-#pragma unroll
-        for (int rr = 0; rr < RB; ++rr) {
-            float v = red_v[rr][0]; int i = red_i[rr][0];
-#pragma unroll
-            for (int w = 1; w < RVQ_WAVES; ++w) argmax_merge(v, i, red_v[rr][w], red_i[rr][w]);
-            if (i == tid) {                                // the winner hands its code over from registers
-#pragma unroll
-                for (int d4 = 0; d4 < D / 4; ++d4)
-                    *reinterpret_cast<float4*>(&q_sh[rr][4 * d4]) = make_float4(e[4 * d4], e[4 * d4 + 1], e[4 * d4 + 2], e[4 * d4 + 3]);
-                if (row0 + rr < n_rows) idx[(size_t)st * n_rows + row0 + rr] = (long long)i + (long long)SIZE * st;
-            }
-        }
-        if (st + 1 < n_q) load_codes(st + 1);              // in flight during the update below
-        __syncthreads();                                   // B: q visible
-        if (owner) {                                       // straight-through + residual (vq_module.py:101-102,143-144)
-            const float q = q_sh[wave][lane];
-            const float qp = rvq_residual_step(r_reg, q);
-            qsum = __fadd_rn(qsum, qp);
-            r2t_sh[lane][wave] = 2.f * r_reg;
-            float v = __fmul_rn(r_reg, r_reg);
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) v = __fadd_rn(v, __shfl_xor(v, off, 64));
-            if (lane == 0) rn_sh[wave] = v;
-        }
-        __syncthreads();                                   // C: residual of the next stage visible
-    }
-    if (zq && owner && row0 + wave < n_rows) zq[(size_t)(row0 + wave) * D + lane] = qsum;
-}
-
 // max over the lanes of a wave by DPP (no LDS traffic): after the four row steps every lane holds its 16-lane row's maximum, after the
 // two broadcast steps lane 63 holds the wave's.
 template <int CTRL, int ROW_MASK>
@@ -269,12 +169,14 @@ __device__ __forceinline__ int wave_argmax_lane(float v, float& vmax) {
     return hit ? __builtin_ctzll(hit) : 0;                 // (no lane compares equal only if every value is NaN)
 }
 
-// ---- v3: v2 with a shorter serial chain per stage (dim == 64, size == 1024, one row per workgroup) ----
-// v2 keeps the 64 code registers until the winner has handed its code over through LDS (every thread folds the 16 candidates, one
-// writes 256 bytes, barrier, the owner reads them).  Here only the owner wave folds the candidates and fetches the winning code from
-// memory (one 64-lane gather of L2-hot lines), so the registers are free as soon as barrier A has passed: all waves request the next
-// stage's 256 KB right there, and they land under the owner's residual update and barrier B.  Two barriers per stage instead of
-// three; per element the same operations in the same order as v1 / v2 (the indices and the sum of codes are bit-identical).
+// ---- v3: the same arithmetic, shorter serial chain per stage (dim == 64, size == 1024, one row per workgroup) ----
+// One thread = one code, its 64 components live in REGISTERS for the stage: all 64 component loads of a stage are in flight at once
+// (the general kernel above: four dependent batches of 16).  The owner wave (wave 0, lane = dimension) keeps r and the running sum of q'
+// in registers, folds the 16 per-wave candidates and fetches the winning code from memory (one 64-lane gather of L2-hot lines), so the
+// code registers are free as soon as barrier A has passed: all waves request the next stage's 256 KB right there, and they land under
+// the owner's residual update and barrier B.  Two barriers per stage instead of five; per element the same operations in the same
+// order as the general kernel (ascending-d fmaf chain, the same butterfly for |r|^2, the same (value, index) merges): the indices and
+// the sum of codes are bit-identical.
 __global__ __launch_bounds__(RVQ_THREADS) void rvq_encode_v3_kernel(const float* __restrict__ z, const float* __restrict__ embed,
                                                                     const float* __restrict__ enorm, long long* __restrict__ idx,
                                                                     float* __restrict__ zq, int n_rows, int n_q) {
@@ -319,7 +221,7 @@ __global__ __launch_bounds__(RVQ_THREADS) void rvq_encode_v3_kernel(const float*
     if (wave == 0) {
         r_reg = z[(size_t)row * D + lane];
         r2_sh[lane] = 2.f * r_reg;
-        float v = __fmul_rn(r_reg, r_reg);                 // flatten.pow(2).sum(1): the butterfly of v1
+        float v = __fmul_rn(r_reg, r_reg);                 // flatten.pow(2).sum(1): the butterfly of rvq_encode_kernel
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) v = __fadd_rn(v, __shfl_xor(v, off, 64));
         if (lane == 0) rn_sh = v;
@@ -381,30 +283,19 @@ __global__ __launch_bounds__(RVQ_THREADS) void rvq_encode_v3_kernel(const float*
 // folds the candidates of row r, fetches its winner, updates its residual), and a launch takes 256 / R workgroups.  Round 3 measured
 // the naive form (rows one after the other, barriers per row) at +1.9 us per extra row and stage; batched, an extra row costs the 64
 // FMAs and one DPP reduction per wave.
-// rows per workgroup of the v4 kernel (ADK_RVQ_ROWS / adk_set_option("rvq_rows"): 0 = v3 at every row count, 2, 4, 1 (default) = 2 up
-// to 512 rows and 4 above: one dispatch round of 256 workgroups each) and the row count from which it takes over (ADK_RVQ_V4_MIN /
-// "rvq_v4_min": default 192 -- below, a workgroup per row is a partial round and faster: 26-28 us against 31.6).
+// rows per workgroup of the v4 kernel (adk_set_option("rvq_rows"): 0 = v3 at every row count, 2, 4, 1 (default) = 2 up
+// to 512 rows and 4 above: one dispatch round of 256 workgroups each) and the row count from which it takes over
+// ("rvq_v4_min": default 192 -- below, a workgroup per row is a partial round and faster: 26-28 us against 31.6).
 // Measured alone on the chip (tools/rvq_time.py, us per launch of 8 stages; rows/wg 1 = v3 to 256 rows, the first-round kernel above):
 //   rows    1/wg   2/wg   4/wg        in the three-stream pipeline at 256 rows, 2/wg against 1/wg: 282.5 k against 275.7 k frames/s
 //    256    31.1   31.6   42.9        (same box, alternating): half the workgroups, half the code bytes pulled through the L2s
 //    512    78.3   36.5   42.9
 //   1024    79.3   66.3   46.7
-// (atomics: adk_set_option may be called from another host thread than the one that launches; the environment is read exactly once)
+// (atomics: adk_set_option may be called from another host thread than the one that launches)
 static std::atomic<int> g_rvq_rows{1}, g_rvq_v4_min{192};
-static std::once_flag g_rvq_env_once;
-static void rvq_read_env() {
-    std::call_once(g_rvq_env_once, [] {
-        const char* e = getenv("ADK_RVQ_ROWS");
-        const int v = e ? atoi(e) : 1;
-        g_rvq_rows = (v == 0 || v == 2 || v == 4) ? v : 1;
-        e = getenv("ADK_RVQ_V4_MIN");
-        if (e) { const int m = atoi(e); g_rvq_v4_min = m < 1 ? 1 : m; }        // clamped as rvq_set_option does: 0 rows never reach the v4 grid
-    });
-}
 int rvq_set_option(const char* name, int value) {
-    rvq_read_env();
     if (!strcmp(name, "rvq_rows")) { if (value != 0 && value != 1 && value != 2 && value != 4) return -1; g_rvq_rows = value; return 0; }
-    if (!strcmp(name, "rvq_v4_min")) { g_rvq_v4_min = value < 1 ? 1 : value; return 0; }
+    if (!strcmp(name, "rvq_v4_min")) { g_rvq_v4_min = value < 1 ? 1 : value; return 0; }        // (0 rows never reach the v4 grid)
     return 1;
 }
 
@@ -441,7 +332,7 @@ __global__ __launch_bounds__(RVQ_THREADS) void rvq_encode_v4_kernel(const float*
     if (owner) {
         r_reg = z[(size_t)my_row * D + lane];
         r2_sh[wave >> 1][2 * lane + (wave & 1)] = 2.f * r_reg;
-        float v = __fmul_rn(r_reg, r_reg);                 // flatten.pow(2).sum(1): the butterfly of v1
+        float v = __fmul_rn(r_reg, r_reg);                 // flatten.pow(2).sum(1): the butterfly of rvq_encode_kernel
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) v = __fadd_rn(v, __shfl_xor(v, off, 64));
         if (lane == 0) rn_sh[wave] = v;
@@ -601,41 +492,27 @@ extern "C" int adk_rvq_encode(const float* z, const float* embed, const float* e
     if (n_rows == 0) return ADK_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
     DeviceGuard guard(device_of(z));
-    static int variant = -1;                              // ADK_RVQ_V1=1: the first-round kernel, ADK_RVQ_V=2: the round-2 one (A/B and cross-checks)
-    static int rb_env = 0;                                // ADK_RVQ_MAXROWS: largest row count the v2 kernel takes (tuning; default 256)
-    if (variant < 0) {
-        const char* e = getenv("ADK_RVQ_V1"); variant = (e && atoi(e) == 1) ? 1 : 3;
-        e = getenv("ADK_RVQ_V"); if (e && variant != 1 && atoi(e) >= 1 && atoi(e) <= 3) variant = atoi(e);
-        e = getenv("ADK_RVQ_MAXROWS"); rb_env = e ? atoi(e) : 0;
-    }
-    rvq_read_env();
-    const int rows_opt = g_rvq_rows.load(), v4_min = g_rvq_v4_min.load();
-    const int v4_rows = rows_opt == 1 ? (n_rows > 512 ? 4 : 2) : rows_opt;
-    if (variant == 3 && v4_rows > 0 && dim == 64 && size == 1024 && n_rows >= v4_min) {
-        if (v4_rows == 2)
-            hipLaunchKernelGGL(rvq_encode_v4_kernel<2>, dim3((n_rows + 1) / 2), dim3(RVQ_THREADS), 0, s, z, embed, enorm, reinterpret_cast<long long*>(idx), zq, n_rows, n_q);
-        else
-            hipLaunchKernelGGL(rvq_encode_v4_kernel<4>, dim3((n_rows + 3) / 4), dim3(RVQ_THREADS), 0, s, z, embed, enorm, reinterpret_cast<long long*>(idx), zq, n_rows, n_q);
-        ADK_HIP_CHECK(hipGetLastError());
-        return ADK_OK;
-    }
-    if (variant >= 2 && dim == 64 && size == 1024 && n_rows <= (rb_env > 0 ? rb_env : 256)) {
-        if (variant == 3) {
-            // helper blocks for few rows (see the kernel head; ADK_RVQ_HELPERS per XCD, 0 = none)
-            static const int n_help = [] { const char* e = getenv("ADK_RVQ_HELPERS"); const int v = e ? atoi(e) : 2; return v < 0 ? 0 : (v > 8 ? 8 : v); }();
-            const unsigned grid3 = (n_help > 0 && n_rows <= 64) ? (unsigned)(((n_rows + 7) & ~7) + 8 * n_help) : (unsigned)n_rows;
+    if (dim == 64 && size == 1024) {
+        const int rows_opt = g_rvq_rows.load(), v4_min = g_rvq_v4_min.load();
+        const int v4_rows = rows_opt == 1 ? (n_rows > 512 ? 4 : 2) : rows_opt;
+        if (v4_rows > 0 && n_rows >= v4_min) {
+            if (v4_rows == 2)
+                hipLaunchKernelGGL(rvq_encode_v4_kernel<2>, dim3((n_rows + 1) / 2), dim3(RVQ_THREADS), 0, s, z, embed, enorm, reinterpret_cast<long long*>(idx), zq, n_rows, n_q);
+            else
+                hipLaunchKernelGGL(rvq_encode_v4_kernel<4>, dim3((n_rows + 3) / 4), dim3(RVQ_THREADS), 0, s, z, embed, enorm, reinterpret_cast<long long*>(idx), zq, n_rows, n_q);
+            ADK_HIP_CHECK(hipGetLastError());
+            return ADK_OK;
+        }
+        // one workgroup per row: one dispatch round up to 256 rows (at 512 rows = two rounds it only ties with the general kernel below,
+        // because each workgroup streams the 2 MB of codes from L2)
+        if (n_rows <= 256) {
+            constexpr int kHelpers = 2;                   // helper blocks per XCD for few rows (see the kernel head)
+            const unsigned grid3 = n_rows <= 64 ? (unsigned)(((n_rows + 7) & ~7) + 8 * kHelpers) : (unsigned)n_rows;
             hipLaunchKernelGGL(rvq_encode_v3_kernel, dim3(grid3), dim3(RVQ_THREADS), 0, s, z, embed, enorm,
                                reinterpret_cast<long long*>(idx), zq, n_rows, n_q);
             ADK_HIP_CHECK(hipGetLastError());
             return ADK_OK;
         }
-        // the latency kernel: one workgroup per row -- one dispatch round up to 256 rows (measured 37 us for 1..32 rows, 43 us
-        // for 256, against 77-78 us of the first-round kernel; at 512 rows = two rounds it only ties, 80 vs 79 us, because each
-        // workgroup streams the 2 MB of codes from L2, so the 4-rows-per-workgroup kernel below keeps the large row counts)
-        hipLaunchKernelGGL(rvq_encode_v2_kernel<1>, dim3(n_rows), dim3(RVQ_THREADS), 0, s, z, embed, enorm,
-                           reinterpret_cast<long long*>(idx), zq, n_rows, n_q);
-        ADK_HIP_CHECK(hipGetLastError());
-        return ADK_OK;
     }
     constexpr int RB = 4;
     hipLaunchKernelGGL(rvq_encode_kernel<RB>, dim3((n_rows + RB - 1) / RB), dim3(RVQ_THREADS), 0, s, z, embed, enorm,

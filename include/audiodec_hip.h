@@ -66,14 +66,14 @@ int adk_abi_version(void);
  * reading synchronises those devices and clears the words.  The Python facade turns a set bit
  * into an exception at its synchronisation points (audiodec_amd/native.py: raise_on_device_flags) */
 int adk_debug_flags(int32_t* out);
-/* tuning hook: force the MFMA conv tile config (0..6), -1 = heuristic (also env ADK_CONV_CFG) */
+/* tuning hook: force the stream-K conv tile config; -1 = heuristic (the default).  0: 128x64 (the split-f16 kernel only: the exact-f32
+ * kernel has no such build and keeps its own choice), 2: 64x64, 4: 32x128.  ADK_ERR_ARG for any other id. */
 int adk_set_conv_cfg(int32_t cfg);
 /* tuning / test hook: named process-wide integer options, read at every launch decision.
  *   "chain_max_channels"  residual chains (adk_op_desc.chain) run as one launch only up to this many channels per group
  *                         (default 128 = every chain the kernel takes; 64: not the 128-channel ones; 0: never -- the ops of a
  *                         chain are then launched one by one, as with ADK_CHAIN=0).  State rings are compatible either way:
  *                         the value may change between two steps of a running program.
- *   "chain_min_channels"  ... and from this many channels per group (default 0)
  *   "chain_min_blocks"    ... and only for launches of at least this many (stream, group) pairs (default 0: always.  Until round 4 the
  *                         default was 160 -- with the chain kernels of that time the per-op launches, which spread a stream's time tiles
  *                         over many CUs, were faster below it; now the chain is faster at every launch size: 1 stream 0.74 -> 0.71 ms per
@@ -83,10 +83,10 @@ int adk_set_conv_cfg(int32_t cfg);
  *                         rows, 4 above; 0: the round-3 kernels at every row count.  Indices and zq are bit-identical either way.
  *   "rvq_v4_min"          see above
  *   "gv16_max_columns"    convs of at most this many columns (streams x steps per call) run as conv_gv16 (csrc/conv_mfma.hip: one wave per
- *                         32-row x 32-column output tile and K slice, no LDS) instead of the stream-K kernel; default 32, 0 = never
- *                         (also env ADK_GV16_MAXN).  Results of the two kernels agree to f32 round-off, not bit for bit.
- *   "conv_ou16", "conv_oc16", "conv_cin1w"   0: the op pairs these launches cover run as two launches again (defaults 1; also env ADK_CONV_OU16,
- *                         ADK_CONV_OC16, ADK_CONV_CIN1W): conv_out + the last up-sampler (csrc/conv_ou16.hip: f32 round-off against the two-launch
+ *                         32-row x 32-column output tile and K slice, no LDS) instead of the stream-K kernel; default 32, 0 = never.
+ *                         Results of the two kernels agree to f32 round-off, not bit for bit.
+ *   "conv_ou16", "conv_oc16", "conv_cin1w"   0: the op pairs these launches cover run as two launches again (defaults 1):
+ *                         conv_out + the last up-sampler (csrc/conv_ou16.hip: f32 round-off against the two-launch
  *                         form), the last conv_out + the output conv (csrc/conv_oc16.hip), the encoder's ring write + its Cin = 1 conv
  *                         (csrc/conv_direct.hip: bit-identical).  A/B measurements and the tests that compare the two forms.
  * ADK_ERR_ARG for an unknown name. */

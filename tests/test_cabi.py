@@ -173,3 +173,33 @@ def test_streamk_plan_covers_every_work_unit_once(lib):
     assert lib.adk_streamk_plan(200, 6, 0, plan) == 0 and list(plan)[:3] == [200, 1, 0]
     assert lib.adk_streamk_plan(300, 22, 0, plan) == 0 and list(plan)[:3] == [512, 0, 0]
     assert lib.adk_streamk_plan(0, 4, 0, plan) != 0 and lib.adk_streamk_range_start(10, 4, plan, 10 ** 6) == -1
+
+
+def test_conv_cfg_takes_only_the_built_tile_configs(lib):
+    """adk_set_conv_cfg: -1 (heuristic) and the three tile configs the library builds; every other id is ADK_ERR_ARG with a message
+    and leaves the choice as it was.  The option chain_min_channels is gone."""
+    try:
+        for cfg in (-1, 0, 2, 4):
+            assert lib.adk_set_conv_cfg(cfg) == 0, (cfg, lib.adk_last_error())
+        for cfg in (1, 3, 5, 6, 7):
+            assert lib.adk_set_conv_cfg(cfg) == -1 and b"adk_set_conv_cfg" in lib.adk_last_error(), cfg
+    finally:
+        assert lib.adk_set_conv_cfg(-1) == 0
+    assert lib.adk_set_option(b"chain_min_channels", 0) == -1 and b"unknown option" in lib.adk_last_error()
+
+
+def test_streamk_plan_ignores_the_retired_environment_knobs(lib):
+    """The stream-K schedule is compile-time constants: a fresh process that has the retired tuning variables set gets the plans
+    test_streamk_plan_covers_every_work_unit_once pins for the benched layers."""
+    import json
+    import sys
+    code = ("import ctypes as C, json, sys; sys.path.insert(0, sys.argv[1]); from audiodec_amd import native; lib = native.lib(); "
+            "plan = (C.c_int32 * 4)(); out = []\n"
+            "for tiles, chunks in ((240, 44), (200, 6), (300, 22)):\n"
+            "    assert lib.adk_streamk_plan(tiles, chunks, 0, plan) == 0; out.append(list(plan))\n"
+            "print(json.dumps(out))")
+    env = dict(os.environ, ADK_CONV_MAX_SPLIT="1", ADK_CONV_MIN_UNITS="7", ADK_CONV_ALIGNED="0", ADK_CONV_OCC="1")
+    r = subprocess.run([sys.executable, "-c", code, ROOT], capture_output=True, text=True, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    plans = json.loads(r.stdout.strip().splitlines()[-1])
+    assert plans[0] == [480, 2, 0, 20] and plans[1][:3] == [200, 1, 0] and plans[2][:3] == [512, 0, 0], plans

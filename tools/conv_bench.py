@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of one fused causal conv launch (tuning aid, not part of the product).
 
-usage: conv_bench.py [--shape s0|s1|s2|s3|...] [--cfg -1..5] [--batch 256] [--iters 50]
+usage: conv_bench.py [--shape s0|s1|s2|s3|...] [--cfg -1|0|2|4] [--batch 256] [--iters 50]
 """
 import argparse
 import ctypes as C
@@ -51,7 +51,7 @@ def run(shape, cfg, B, iters, impl=native.IMPL_MFMA, check=False):
     d.act_in, d.act_in_slope, d.act_out = act, 0.1, 0
     wf = (pack_split16(w.cpu(), groups) if impl in (native.IMPL_SPLIT16, native.IMPL_SPLIT16_ROWS, native.IMPL_SPLIT16_SK) else pack_mfma(w.cpu(), groups)).to(dev)
     d.w, d.w_frag, d.bias = w.data_ptr(), wf.data_ptr(), bias.data_ptr()
-    lib.adk_set_conv_cfg(cfg)
+    native.check(lib.adk_set_conv_cfg(cfg), "adk_set_conv_cfg")       # -1 heuristic, 0 (split-f16 only) / 2 / 4
     st = native.current_stream(dev)
     vin, vout, vres = view(ring, rows, cin_t, hist), view(out, t_out * up, cout_real, 0), view(None, 0, 0, 0)
 
@@ -82,7 +82,7 @@ def run(shape, cfg, B, iters, impl=native.IMPL_MFMA, check=False):
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--shape", default="s0,s1,s2,s3")
-    ap.add_argument("--cfg", default="-1")
+    ap.add_argument("--cfg", default="-1", help="comma list of tile configs: -1 heuristic, 0 = 128x64 (split-f16 only), 2 = 64x64, 4 = 32x128")
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--impl", type=int, default=native.IMPL_MFMA, help="0 auto, 2 stream-K, 3 rows-in-LDS; split-f16: 4 auto, 5 rows-in-LDS, 6 stream-K")

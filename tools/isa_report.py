@@ -20,7 +20,7 @@ IN_USE = {"Li32ELi2ELi11ELi11ELi3ELi1ELi2ELi2ELb0ELi0ELi0E": "vocoder stage 3 (3
           "Li32ELi1ELi7ELi1ELi3ELi1ELi2ELi2ELb1ELi0ELi0E": "encoder block 0 (32 ch, 3 tiles)",
           "Li64ELi1ELi7ELi1ELi2ELi1ELi3ELi1ELb1ELi0ELi3E": "encoder block 1 (64 ch, weight ring)",
           "Li128ELi1ELi7ELi1ELi2ELi2ELi2ELi3ELb1ELi4ELi0E": "encoder block 2 (128 ch)",
-          "Li64ELi2ELi11ELi11ELi2ELi1ELi3ELi2ELb1ELi0ELi0E": "(round 3) vocoder stage 2 without the ring: ADK_RB16_RING=0"}
+          "Li64ELi2ELi11ELi11ELi2ELi1ELi3ELi2ELb1ELi0ELi0E": "vocoder stage 2 without the ring (launches of <= 128 workgroups; every launch in round 3)"}
 
 
 def main():
