@@ -122,6 +122,11 @@ int launch_conv_up16(const ConvArgs& a, hipStream_t s);
 int launch_conv_sk16(const ConvArgs& a, hipStream_t s, Workspace& ws);   // split-f16 stream-K (same shapes as launch_conv_mfma)
 int conv_sk16_pick(const ConvArgs& a);
 bool conv_gv16_preferred(const ConvArgs& a);        // few columns (n_total <= 32): the GEMV-shaped kernel launch_conv_sk16 hands them to
+// rows-once-in-LDS whole-tile kernel for wide groups at several steps per stream (conv_rk16.hip); launch_conv_sk16 hands it the calls it prefers
+bool conv_rk16_eligible(const ConvArgs& a);         // the shape class: a function of the conv arguments alone
+bool conv_rk16_preferred(const ConvArgs& a);        // ... and option "conv_rk16" allows it, and the launch fills the chip
+void conv_rk16_set(int value);                      // option "conv_rk16": 0 never, 1 launches that fill the chip (default), 2 every eligible launch
+int launch_conv_rk16(const ConvArgs& a, hipStream_t s);      // ADK_ERR_STATE: not eligible
 int conv_set_option(const char* name, int value);  // conv_mfma.hip: 0 = set, 1 = not a conv option
 int rvq_set_option(const char* name, int value);   // rvq.hip: 0 = set, 1 = not an RVQ option, -1 = bad value
 int rvq_ema_set_option(const char* name, int value);   // rvq_ema.hip: same convention

@@ -135,6 +135,9 @@ static std::string conv_kernel_name(const ConvArgs& a, int impl) {
         const bool rows = impl == ADK_IMPL_SPLIT16_ROWS || (impl == ADK_IMPL_SPLIT16 && conv_rl16_preferred(a));
         if (rows) return a.cin_g == 32 ? "conv_rl16<32>" : "conv_rl16<64>";
         if (conv_gv16_preferred(a)) return "conv_gv16<32>";
+        // conv_rk16: inside launch_conv_sk16, with the stream-K kernel's epilogue -- named as a member of that family (an op that writes a
+        // shadow ring is expected to describe itself as one)
+        if (conv_rk16_preferred(a)) return "conv_sk16<rk16 64x64>";
         return std::string(conv_mfma_cfg_name(conv_sk16_pick(a))).replace(0, 7, "conv_sk16");
     }
     const bool mf = impl != ADK_IMPL_DIRECT && conv_mfma_supported(a) && (impl == ADK_IMPL_MFMA || impl == ADK_IMPL_MFMA_ROWS || a.groups * a.cout_g >= 32);

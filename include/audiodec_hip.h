@@ -89,6 +89,13 @@ int adk_set_conv_cfg(int32_t cfg);
  *                         conv_out + the last up-sampler (csrc/conv_ou16.hip: f32 round-off against the two-launch
  *                         form), the last conv_out + the output conv (csrc/conv_oc16.hip), the encoder's ring write + its Cin = 1 conv
  *                         (csrc/conv_direct.hip: bit-identical).  A/B measurements and the tests that compare the two forms.
+ *   "conv_rk16"           split-f16 convs of wide groups (>= 128 input channels per group, K 7 or 11, stride 1) whose taps share input rows
+ *                         across the steps of a call run as conv_rk16 (csrc/conv_rk16.hip: whole 64 x 64 tiles, rows staged once in LDS,
+ *                         no K split) instead of the stream-K kernel.  1 (default; the environment's ADK_CONV_RK16 sets another one):
+ *                         launches of at least 192 tiles, i.e. that fill the chip; 2: every launch of the shape class (tests); 0: never.
+ *                         The rings and shadow rings the two kernels leave are interchangeable, the value may change between two calls;
+ *                         results agree to f32 round-off, not bit for bit.  adk_causal_conv_describe / adk_program_describe_op name the
+ *                         launch "conv_sk16<rk16 64x64>".
  * ADK_ERR_ARG for an unknown name. */
 int adk_set_option(const char* name, int32_t value);
 /* Introspection of the stream-K launch schedule (pure host logic, no device needed; used by the CPU tests): a matrix-core conv

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of one fused causal conv launch (tuning aid, not part of the product).
 
-usage: conv_bench.py [--shape s0|s1|s2|s3|...] [--cfg -1|0|2|4] [--batch 256] [--iters 50]
+usage: conv_bench.py [--shape s0|s0d1|s1|s2|s3|...] [--cfg -1|0|2|4] [--batch 256] [--iters 50] [--set conv_rk16=0,conv_rk16=1]
 """
 import argparse
 import ctypes as C
@@ -16,7 +16,7 @@ from audiodec_amd.native import ConvDesc, RingView  # noqa: E402
 from audiodec_amd.program import pack_mfma, pack_split16  # noqa: E402
 
 SHAPES = {  # cin_g, cout_g, groups, taps, stride, dil, t_out, up, act
-    "s0": (256, 256, 3, 11, 1, 5, 5, 1, 2), "s1": (128, 128, 3, 11, 1, 5, 25, 1, 2),
+    "s0": (256, 256, 3, 11, 1, 5, 5, 1, 2), "s0d1": (256, 256, 3, 11, 1, 1, 5, 1, 2), "s1": (128, 128, 3, 11, 1, 5, 25, 1, 2),
     "s2": (64, 64, 3, 11, 1, 5, 100, 1, 2), "s3": (32, 32, 3, 11, 1, 5, 300, 1, 2),
     "e3": (256, 256, 1, 7, 1, 9, 5, 1, 1), "e2": (128, 128, 1, 7, 1, 9, 25, 1, 1),
     "e1": (64, 64, 1, 7, 1, 9, 100, 1, 1), "e0": (32, 32, 1, 7, 1, 9, 300, 1, 1),
@@ -87,8 +87,14 @@ if __name__ == "__main__":
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--impl", type=int, default=native.IMPL_MFMA, help="0 auto, 2 stream-K, 3 rows-in-LDS; split-f16: 4 auto, 5 rows-in-LDS, 6 stream-K")
     ap.add_argument("--check", action="store_true", help="compare the output with the f32 stream-K kernel")
+    ap.add_argument("--set", default="", help="comma list of name=value library options (adk_set_option), each timed in turn, e.g. conv_rk16=0,conv_rk16=1")
+    ap.add_argument("--repeat", type=int, default=1, help="time the whole list this many times (alternating the options)")
     a = ap.parse_args()
-    for sh in a.shape.split(","):
-        for cfg in a.cfg.split(","):
-            us, tf = run(sh, int(cfg), a.batch, a.iters, a.impl, a.check)
-            print(f"{sh:5s} impl {a.impl} cfg {cfg:>2s}  B={a.batch}  {us:9.1f} us  {tf:7.1f} TFLOP/s", flush=True)
+    for _ in range(a.repeat):
+        for sh in a.shape.split(","):
+            for cfg in a.cfg.split(","):
+                for opt in a.set.split(","):
+                    if opt:
+                        native.set_option(opt.split("=")[0], int(opt.split("=")[1]))
+                    us, tf = run(sh, int(cfg), a.batch, a.iters, a.impl, a.check)
+                    print(f"{sh:5s} impl {a.impl} cfg {cfg:>2s} {opt:14s} B={a.batch}  {us:9.1f} us  {tf:7.1f} TFLOP/s", flush=True)
