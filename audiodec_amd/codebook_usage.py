@@ -76,11 +76,7 @@ class CodebookUsage:
         return self
 
     def update(self, z, idx):
-        for t in (z, idx):
-            lg = lazy_guard.log_of(t)
-            if lg is not None:
-                lg.settle()
-        z, idx = lazy_guard.plain(z), lazy_guard.plain(idx)
+        z, idx = lazy_guard.settled(z), lazy_guard.settled(idx)
         if z.dim() != 3 or z.shape[1] != self.dim:
             raise ValueError(f"update: z must be (B, {self.dim}, T), got {tuple(z.shape)}")
         B, D, T = z.shape

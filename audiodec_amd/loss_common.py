@@ -5,7 +5,8 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import lazy_guard, native
+from . import native
+from .lazy_guard import settled as _settled
 
 
 def num_frames(n_samples, hop_size):
@@ -15,13 +16,6 @@ def num_frames(n_samples, hop_size):
 
 def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _settled(t):
-    lg = lazy_guard.log_of(t)
-    if lg is not None:
-        lg.settle()
-    return lazy_guard.plain(t)
 
 
 def _no_grad_inputs(*ts):

@@ -23,16 +23,21 @@ its input ring (``ADK_STEP_REPLAY``).  Exact, for the reason the synchronous rep
 steps wrote.  A result is FINAL once ``exit()`` / ``settle()`` has returned or ``depth`` further steps were taken --
 which is when a caller may let it leave the device.
 
+The log of unverified batches -- the loop that polls, when the host waits, what a failure hands to the repair -- is
+``guard_log.GuardLog``, the one the direct calls' ``lazy_guard.CallLog`` is built on too; the rewind and the demotion are
+``guard_log.rewind_and_demote``.  What is this module's own is the device side (``_poll``, ``_drain``) and how batches are
+run again (``_repair``, ``_repeat``).
+
 ``guard=False`` generators run through the same schedule unchecked (failures surface at the caller's next
 ``native.raise_on_device_flags``), as bench.py's `unguarded` leg does.
 """
-import collections
 import time
 import warnings
 
 import torch
 
 from . import lazy_guard, native
+from .guard_log import GuardLog, rewind_and_demote
 
 _STREAM_POOL = {}
 
@@ -55,75 +60,6 @@ class _Batch:
         self.x = self.z = self.idx = self.y = None
         self.steps = []          # (program, frames, ticket), in issue order
         self.units = units       # frames per stream of this batch: what a rewind of it takes out of the rings' extra rows
-
-
-class GuardLog:
-    """Bookkeeping of the deferred guard, free of torch / HIP: which batches are unverified, when to wait, what to redo.
-
-    `poll(program, ticket, block) -> (done, flags)`; `repair(batches, flags_by_program, culprit)` is called with the unverified
-    batches from the first bad one on (oldest first) and must leave them correct.  `culprit` = the first program, in issue order,
-    that reported in the first bad batch: programs behind it (and the same programs in later batches) may only have seen its garbage."""
-
-    def __init__(self, depth, poll, repair, drain, budget=None):
-        """depth: most batches unverified at a time; budget: most UNITS (frames per stream, summed over the unverified batches) -- what the
-        rings can be rewound by; None = no limit besides depth."""
-        assert depth >= 1
-        self.depth, self._poll, self._repair, self._drain = int(depth), poll, repair, drain
-        self.budget = budget
-        self.pending = collections.deque()
-        self.verified = 0            # batches found clean (or repaired) so far
-        self.repairs = 0
-        self.waits = 0               # times the host had to wait for the oldest batch (log full)
-
-    def push(self, batch):
-        self.pending.append(batch)
-
-    def units_pending(self):
-        return sum(b.units for b in self.pending)
-
-    def collect(self, block=False, incoming=0):
-        """Retire the batches whose posts have completed; block=True -- or a log that is full, or that could not be rewound any more with the
-        `incoming` units of the batch about to be issued on top -- waits for the oldest first."""
-        while self.pending:
-            must = block or len(self.pending) >= self.depth or (self.budget is not None and self.units_pending() + incoming > self.budget)
-            b = self.pending[0]
-            found, ready = [], True
-            for prog, _frames, ticket in b.steps:
-                done, fl = self._poll(prog, ticket, False)
-                if not done and must:
-                    self.waits += 0 if block else 1
-                    done, fl = self._poll(prog, ticket, True)
-                if not done:
-                    ready = False
-                    break
-                if fl:
-                    found.append((prog, fl))
-            if found:
-                # (a poll reads AND clears the program's word -- ABI 14 --, so what was found is handed on; the posts of the head batch that were
-                # not reached are read by _recover.  A word may already hold what a LATER batch's step reported: the blame can only be early.)
-                self._recover(found)
-                return
-            if not ready:
-                return
-            self.pending.popleft()
-            self.verified += 1
-
-    def _recover(self, found):
-        """found: [(program, flags)] read from posts of the OLDEST unverified batch, in issue order: that batch is the first bad one."""
-        self._drain()                                   # everything issued has finished: every post can be read
-        batches = list(self.pending)
-        by_prog, culprit = {}, found[0][0]
-        for prog, fl in found:
-            by_prog[prog] = by_prog.get(prog, 0) | fl
-        for b in batches:                               # the rest of the words: read (and thereby cleared) too
-            for prog, _frames, ticket in b.steps:
-                _done, fl = self._poll(prog, ticket, True)
-                if fl:
-                    by_prog[prog] = by_prog.get(prog, 0) | fl
-        self.pending.clear()
-        self._repair(batches, by_prog, culprit)
-        self.verified += len(batches)
-        self.repairs += 1
 
 
 class StreamingPipeline:
@@ -158,6 +94,7 @@ class StreamingPipeline:
         self.depth = room if self.deferred else 0
         # what the rings can be rewound by, in frames per stream: (rewind_depth + 1) x max_frames (rows = hist + that many frames)
         self.budget = min([(getattr(g, "rewind_depth", 0) + 1) * getattr(g, "max_frames", 1) for g in gens]) if self.deferred else 0
+        self.max_frames = min([getattr(g, "max_frames", 1) for g in gens])      # hops per program step: a batch of more takes several posts
         self.log = GuardLog(self.depth, self._poll, self._repair, self._drain, self.budget) if self.deferred else None
         # host-side accounting (seconds, since construction / reset_host_times()): t_issue = handing a batch's launches to the runtime,
         # t_guard = reading / waiting for the posts of older batches at the entry of step() -- what a rank's Python costs per step
@@ -225,7 +162,7 @@ class StreamingPipeline:
             y = self._issue(x, None)
             self.t_issue += time.perf_counter() - t0
             return y
-        self.log.collect(incoming=frames)
+        self.log.collect(incoming=frames, posts=-(-frames // self.max_frames))
         t1 = time.perf_counter()
         self.t_guard += t1 - t0
         b = _Batch(frames)
@@ -296,17 +233,7 @@ class StreamingPipeline:
         after -- may be nothing but its garbage), run the batches again serially on the current stream into the tensors already
         handed out.  The generators' own synchronous guard checks every repeated step: a program that overflows on clean input
         too is demoted there, at the step that does it."""
-        other = 0
-        for fl in by_prog.values():
-            other |= fl & ~native.FLAG_F16_OVERFLOW
-        native.raise_for_flags(other, "StreamingPipeline")
-        for b in reversed(batches):
-            for prog, frames, _t in reversed(b.steps):
-                prog.rewind(frames)
-        if by_prog.get(culprit, 0) & native.FLAG_F16_OVERFLOW:
-            if not culprit.split16 or culprit.twin_builder is None or culprit.demoted:
-                raise native.NativeError("StreamingPipeline: a program without an exact-f32 twin reported an f16 range overflow")
-            culprit.demote()
+        rewind_and_demote(batches, by_prog, culprit, "StreamingPipeline")
         gens = [g for g in (self.tx, self.rx, self.dec) if g is not None]
         modes = [getattr(g, "guard_mode", None) for g in gens]
         for g in gens:

@@ -17,6 +17,7 @@ the reference's.
 import ctypes as C
 import math
 import os
+import threading
 
 import torch
 
@@ -140,12 +141,14 @@ class _StreamBase:
 
     def _call_log(self):
         """The log a direct call is recorded in, or None: guard off / mode "sync" / a pipeline owns the guard (_defer) / the rings carry no
-        rows to rewind by / offline programs / the call is a repeat made by the log itself."""
+        rows to rewind by / offline programs / the call is a repeat made by the log itself (on the repairing thread: any other thread's call
+        waits on the log's lock until the repair is over and is logged then)."""
         if not self.guard or self.guard_mode != "lazy" or self._defer is not None or self.rewind_depth < 1 or self.offline:
             return None
         if self._log is None:
             self._log = lazy_guard.CallLog(self._dev())
-        return None if self._log.in_redo else self._log
+        redo = self._log.in_redo
+        return None if redo is not None and redo == threading.get_ident() else self._log
 
     def _guarded(self, impl, args, progs, frames):
         log = self._call_log()
@@ -464,10 +467,7 @@ class AutoEncoderStreamGenerator(_StreamBase):
                 raise ValueError("quantizer_forward(ema=...): this generator does not use the CodebookEMA's current table "
                                  "(ema.install(generator) after its last update, or make the CodebookEMA from this generator)")
             self.settle()
-            lg = lazy_guard.log_of(z)
-            if lg is not None:
-                lg.settle()
-            z = lazy_guard.plain(z)
+            z = lazy_guard.settled(z)
             flat = self._quantizer_forward_stats(z)            # [zq | vqloss | perplexity] on this generator's table, as without ema
             B, D, T = z.shape
             n = B * T * D

@@ -7,39 +7,9 @@ import warnings
 import pytest
 import torch
 
-from audiodec_amd import lazy_guard
+from audiodec_amd import lazy_guard, native
 from audiodec_amd.lazy_guard import CallLog, GuardedTensor
-
-
-class FakeProgram:
-    """Posts complete when the fake device clock has passed them (or somebody waits); a post's word is what `fail_at` says for that ticket."""
-
-    def __init__(self, name, rewind_depth=4, max_frames=1, events=None):
-        self.name, self.rewind_depth, self.max_frames = name, rewind_depth, max_frames
-        self.tickets, self.completed, self.fail_at = 0, -1, {}
-        self.blocked = 0
-        self.split16, self.twin_builder, self.demoted = True, object(), False
-        self.events = events if events is not None else []
-
-    def post(self):
-        t = self.tickets
-        self.tickets += 1
-        return t
-
-    def poll_flags(self, ticket, block):
-        if ticket > self.completed:
-            if not block:
-                return False, 0
-            self.blocked += 1
-            self.completed = ticket
-        return True, self.fail_at.get(ticket, 0)
-
-    def rewind(self, frames):
-        self.events.append(("rewind", self.name, frames))
-
-    def demote(self):
-        self.events.append(("demote", self.name))
-        self.split16, self.demoted = False, True
+from guard_fakes import FakeProgram
 
 
 class FakeGen:
@@ -148,6 +118,74 @@ def test_calls_longer_than_the_rings_can_be_rewound_by_run_synchronously():
     log, (g,), events, _ = make(rewind_depth=1)
     out = log.run(g, g._impl, (torch.zeros(1),), [g.prog], 5)       # 5 hops > (1 + 1) x 1
     assert type(out) is torch.Tensor and not log.pending and events[-1] == ("run", "p0", False, True)
+
+
+def test_a_failure_of_the_head_call_found_while_the_log_is_full_is_repaired():
+    """The wait for the oldest call reads AND clears its program's word: what it reads must reach the repair, not be dropped."""
+    log, (g,), events, drained = make(rewind_depth=1)                # 2 hops may be unverified
+    g.prog.fail_at[0] = 8                                            # the first call's step overflows; the device never reports by itself
+    x = torch.zeros(2)
+    ys = []
+    with warnings.catch_warnings(record=True) as w:
+        warnings.simplefilter("always")
+        for n in range(4):
+            ys.append(g.call(x))                                     # (call 2 finds the log full and waits for its head)
+            if n < 2:
+                lazy_guard.plain(ys[n]).fill_(float("nan"))          # what the kernels left of the bad call and the one issued on top of it
+        v = float(ys[3].sum())                                       # one look
+    assert len([i for i in w if issubclass(i.category, RuntimeWarning)]) == 1
+    assert log.repairs == 1 and g.prog.demoted and log.verified == 4 and not log.pending
+    assert v == 2.0 and all(torch.equal(lazy_guard.plain(y), torch.ones(2)) for y in ys)
+
+
+def test_a_program_never_has_more_unread_posts_than_the_native_side_keeps_events_for():
+    n_calls = native.POST_SLOTS + 8
+    log, (g,), _, _ = make(rewind_depth=2 * native.POST_SLOTS - 1)   # (the hop budget does not bind)
+    x = torch.zeros(1)
+    ys = [g.call(x) for _ in range(n_calls)]                         # nothing is looked at, the device never reports by itself;
+    assert g.prog.most_unread <= native.POST_SLOTS and log.waits > 0  # (the fake raises on a poll of a ticket whose event is gone)
+    assert float(ys[-1].sum()) == 1.0 and log.verified == n_calls and not log.pending
+
+
+@pytest.mark.filterwarnings("ignore::RuntimeWarning")
+def test_while_one_thread_repairs_another_threads_look_and_call_wait_for_it():
+    log, (g,), _, _ = make()
+    x = torch.zeros(2)
+    in_redo, go = threading.Event(), threading.Event()
+    run = g._impl
+
+    def impl(x_):
+        if g._defer is None:                                         # the repeat made by the repair: hold it
+            in_redo.set()
+            assert go.wait(60)
+        return run(x_)
+    g._impl = impl
+    y = g.call(x)
+    g.prog.fail_at[0] = 8
+    lazy_guard.plain(y).fill_(float("nan"))
+    done = {}
+
+    def repairer():
+        done["repair"] = float(y.sum())
+
+    def looker():
+        done["look"] = float(y.sum())
+
+    def caller():
+        done["call"] = g.call(x)
+    ts = [threading.Thread(target=f, daemon=True) for f in (repairer, looker, caller)]
+    ts[0].start()
+    assert in_redo.wait(60)                                          # thread 0 is inside the redo, the result half rewritten
+    ts[1].start(); ts[2].start()
+    ts[1].join(0.3); ts[2].join(0.3)
+    early = sorted(k for k in done)
+    go.set()
+    for t in ts:
+        t.join(60)
+    assert not any(t.is_alive() for t in ts)
+    assert early == [], early                                        # neither the look nor the call returned during the repair
+    assert done["repair"] == 2.0 and done["look"] == 2.0 and torch.equal(lazy_guard.plain(y), torch.ones(2))
+    assert type(done["call"]) is GuardedTensor and log.repairs == 1 and log.verified + len(log.pending) == 2
 
 
 def test_two_threads_share_a_log():

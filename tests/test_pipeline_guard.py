@@ -1,30 +1,10 @@
-"""CPU: the bookkeeping of the deferred guard (audiodec_amd/pipeline.py: GuardLog) against fake programs -- which batches are
-retired, when the host waits, what is handed to the repair -- and the host-side contract of StreamingPipeline that needs no device."""
+"""CPU: the bookkeeping of the deferred guard (audiodec_amd/guard_log.py: GuardLog, as pipeline.StreamingPipeline uses it) against fake
+programs -- which batches are retired, when the host waits, what is handed to the repair -- and the host-side contract of
+StreamingPipeline that needs no device."""
 import pytest
 
 from audiodec_amd.pipeline import GuardLog, _Batch
-
-
-class FakeProgram:
-    """Posts complete when the fake device clock has passed them; a post's word is what `fail_at` says for that ticket."""
-
-    def __init__(self, name):
-        self.name, self.tickets, self.fail_at = name, 0, {}
-        self.completed = -1          # tickets <= completed are done
-        self.blocked = 0
-
-    def post(self):
-        t = self.tickets
-        self.tickets += 1
-        return t
-
-    def poll(self, ticket, block):
-        if ticket > self.completed:
-            if not block:
-                return False, 0
-            self.blocked += 1
-            self.completed = ticket      # waiting lets the device get there
-        return True, self.fail_at.get(ticket, 0)
+from guard_fakes import FakeProgram
 
 
 def make_log(depth, progs, repaired, drained):
@@ -75,6 +55,24 @@ def test_a_full_log_waits_for_the_oldest_batch_only():
     assert log.waits == 3 and enc.blocked == 3 and len(log.pending) == 3 and log.verified == 3 and not repaired
 
 
+def test_a_bad_head_batch_found_by_the_wait_of_a_full_log_is_repaired():
+    """The wait for the oldest batch and the read of its word are one poll: what that poll reads (and thereby clears) goes to the repair."""
+    enc, dec = FakeProgram("enc"), FakeProgram("dec")
+    repaired, drained = [], []
+    log = make_log(2, [enc, dec], repaired, drained)
+    enc.fail_at[0] = 8
+    for n in range(2):
+        log.collect()
+        issue(log, [enc, dec], n)                        # the device never reports by itself
+    assert not repaired and len(log.pending) == 2
+    log.collect()                                        # entry of step 2: the log is full, the head is waited for -- and is bad
+    assert log.waits == 2 and enc.blocked == dec.blocked == 1 and drained == [1] and repaired == [([0, 1], {"enc": 8}, "enc")]
+    assert not log.pending and log.verified == 2 and log.repairs == 1
+    issue(log, [enc, dec], 2)
+    log.collect(block=True)
+    assert log.verified == 3 and len(repaired) == 1
+
+
 def test_a_bad_batch_hands_everything_from_it_on_to_the_repair_once():
     enc, dec = FakeProgram("enc"), FakeProgram("dec")
     repaired, drained = [], []
@@ -83,6 +81,8 @@ def test_a_bad_batch_hands_everything_from_it_on_to_the_repair_once():
         log.collect()
         issue(log, [enc, dec], n)
     dec.fail_at[1] = 8                                   # the decoder overflowed in batch 1; batch 2 is already issued
+    enc.completed = dec.completed = 0                    # (a poll reads what the program reported up to the device clock: batch 0 is read
+    log.collect()                                        # while the clock stands at it, or it would -- rightly -- take the blame)
     enc.completed = dec.completed = 1
     log.collect()
     assert drained == [1] and repaired == [([1, 2], {"dec": 8}, "dec")]
