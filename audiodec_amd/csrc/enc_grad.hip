@@ -1,0 +1,404 @@
+// The encoder's training half: the strided down-sampling conv (models/autoencoder/modules/encoder.py:62-68) forward and backward
+// to its input, and the gradient of a causal conv with respect to its weight and bias, for every layer kind of the encoder.
+// Exact f32 on v_mfma_f32_32x32x2_f32; every output element is written once by one thread or one accumulator, nothing is added
+// atomically, and every split of a sum is a function of the shape alone: forward and gradients are bitwise reproducible.
+//
+// a is a conv's INPUT activation as in dec_grad.hip, none or ELU(alpha): a(x) = x > 0 ? x : alpha expm1_neg(x).
+// k kernel, d dilation, s stride, T the input length, T_out = (T - 1) / s + 1; an index outside [0, T) or [0, T_out) is skipped
+// (the causal left padding is predicated loads).
+//
+//   enc_down_kernel:       CausalConv1d.forward for k = 2s, d = 1, no input activation:
+//                            y[b][co][u] = bias[co] + sum_{ci,j} W[co][ci][j] x[b][ci][u s - (k-1-j)]
+//                          conv_gemm_f32's core: M = C_out, K = C_in k (kk = ci k + j), N = B T_out; W is [kk][co].
+//   enc_down_grad_kernel:  dx[b][ci][v] = sum_co sum_{j : (v+k-1-j) % s == 0, u = (v+k-1-j)/s < T_out} W[co][ci][j] dy[b][co][u]
+//                          For k = 2s, v = q s + r has the two taps j0 = (r + s - 1) % s and j0 + s, which read
+//                          u0 = q + (r ? 2 : 1) and u0 - 1.  One GEMM per phase r = blockIdx.z: M = C_in, K = 2 C_out
+//                          (kk = 2 co + tap), N = B count_r, count_r the v < T of phase r; W re-packed to [r][kk][ci].  A phase's
+//                          stores are strided by s.  No structural zero is multiplied.
+//   wgrad_kernel:          dW[co][ci][j] = sum_{b,u} dy[b][co][u] a(x[b][ci][u s - (k-1-j) d]),  db[co] = sum_{b,u} dy[b][co][u]
+//                          GEMM M = C_out, N = C_in k + 1 (n = ci k + j; the last column's tap is 1: db, left out when db is
+//                          not asked for, which saves the 1x1 convs of 2^n channels a whole column tile), reduction over
+//                          rho = b T_out + u.  dy and x are contiguous along u, so the staging threads run along rho and write LDS
+//                          transposed to the MFMA's [rho][m] / [rho][n].  The reduction is cut into S slices of whole 32-deep
+//                          steps (wgrad_plan: a function of the shape only); workgroup (tile, slice) writes its f32 partial tile
+//                          to the workspace [slice][m][n].
+//   wgrad_fold_kernel:     one thread per (m, n): the S partials in ascending slice order in f64, rounded once, stored as
+//                          dW [co][ci][k] (the reference's layout: m (C_in k) + n) or db[m].
+#include "conv_gemm_f32.h"
+
+namespace adk {
+
+constexpr int ENC_ACT_NONE = 0, ENC_ACT_ELU = 1;
+constexpr int WG_KT = 32;                           // reduction depth of one LDS slice of the weight gradient
+constexpr int WG_TARGET_WGS = 512;                  // workgroups a weight-gradient launch aims at (two per CU of 256)
+constexpr int WG_MIN_STEPS = 4;                     // a slice is at least this many 32-deep steps (when there are that many)
+
+// dec_grad.hip's dec_act, restated (that file's code objects stay as they are)
+__device__ __forceinline__ float enc_act(float v, int act, float alpha) {
+    return (act == ENC_ACT_ELU && !(v > 0.f)) ? alpha * expm1_neg(v) : v;
+}
+
+struct EncDown {                                    // x [n_items][c_in][t] -> y [n_items][c_out][t_out]
+    int n_items, c_in, c_out, t, t_out, ksz, stride;
+    long long n_cols;                               // n_items * t_out
+    const float* x; const float* w; const float* bias; float* y;
+};
+struct EncDownGrad {                                // dy [n_items][c_out][t_out] -> dx [n_items][c_in][t]
+    int n_items, c_in, c_out, t, t_out, ksz, stride;
+    long long n_cols;
+    const float* dy; const float* w; float* dx;
+};
+
+struct EncPlainStore {
+    __device__ __forceinline__ void operator()(float* dst, float v, int, float) const { *dst = v; }
+};
+
+struct EncDownSrc {
+    const EncDown& c;
+    long long xbase = 0;
+    int p = -0x40000000;                            // u s; an invalid column fails the bounds test
+    __device__ int k_extent() const { return c.c_in * c.ksz; }
+    __device__ int m_extent() const { return c.c_out; }
+    __device__ long long n_cols() const { return c.n_cols; }
+    __device__ const float* weights() const { return c.w; }
+    __device__ void column(long long col) {
+        if (col < c.n_cols) {
+            const long long item = col / c.t_out;
+            p = (int)(col - item * c.t_out) * c.stride;
+            xbase = item * c.c_in * c.t;
+        }
+    }
+    __device__ float tap(int kk) const {
+        const int ci = kk / c.ksz, tt = p - (c.ksz - 1 - (kk - ci * c.ksz));
+        const bool ok = kk < c.c_in * c.ksz && tt >= 0;                 // tt <= u s <= t - 1
+        return ok ? c.x[xbase + (long long)ci * c.t + tt] : 0.f;
+    }
+    __device__ float* out(long long n) const {
+        const long long item = n / c.t_out;
+        return c.y + item * c.c_out * c.t_out + (n - item * c.t_out);
+    }
+    __device__ long long out_stride() const { return c.t_out; }
+    __device__ int bias_index(int m) const { return m; }
+};
+
+// Phase r = blockIdx.z of the backward: columns are the v = q s + r < t of every item; kk = 2 co + tap reads u0 - tap.
+struct EncDownGradSrc {
+    const EncDownGrad& c;
+    const int r = blockIdx.z;
+    const int cnt = phase_count(c.t, c.stride, r);
+    const int lead = r ? 2 : 1;
+    long long ybase = 0;
+    int q = 0;
+    bool valid = false;
+    __device__ int k_extent() const { return 2 * c.c_out; }
+    __device__ int m_extent() const { return c.c_in; }
+    __device__ long long n_cols() const { return (long long)c.n_items * cnt; }
+    __device__ const float* weights() const { return c.w + (size_t)r * 2 * c.c_out * c.c_in; }
+    __device__ void column(long long col) {
+        if (col < n_cols()) {
+            const long long item = col / cnt;
+            q = (int)(col - item * cnt);
+            ybase = item * c.c_out * c.t_out;
+            valid = true;
+        }
+    }
+    __device__ float tap(int kk) const {
+        const int co = kk >> 1, u = q + lead - (kk & 1);
+        const bool ok = valid && kk < 2 * c.c_out && u < c.t_out;
+        return ok ? c.dy[ybase + (long long)co * c.t_out + u] : 0.f;
+    }
+    __device__ float* out(long long n) const {
+        const long long item = n / cnt;
+        return c.dx + item * c.c_in * c.t + (n - item * cnt) * c.stride + r;
+    }
+    __device__ long long out_stride() const { return c.t; }
+    __device__ int bias_index(int m) const { return m; }
+};
+
+template <int WM, int WN, int TM, int TN>
+__global__ __launch_bounds__(CG_THREADS) void enc_down_kernel(EncDown c) {
+    EncDownSrc src{c};
+    conv_gemm_f32<WM, WN, TM, TN>(src, c.bias, CG_ACT_NONE, 0.f, EncPlainStore{});
+}
+template <int WM, int WN, int TM, int TN>
+__global__ __launch_bounds__(CG_THREADS) void enc_down_grad_kernel(EncDownGrad c) {
+    EncDownGradSrc src{c};
+    conv_gemm_f32<WM, WN, TM, TN>(src, nullptr, CG_ACT_NONE, 0.f, EncPlainStore{});
+}
+
+// ---- the weight gradient ----
+struct WGrad {
+    int n_items, c_in, c_out, t, t_out, ksz, dil, stride, act;
+    float alpha;
+    int ck;                                         // c_in * ksz: columns 0 .. ck - 1 are dW's, column ck is db's
+    int nc_live;                                    // columns computed: ck + 1, or ck when db is not asked for
+    int red;                                        // n_items * t_out: the reduction length
+    int steps_per, slices;                          // 32-deep steps of one slice, and S
+    const float* dy; const float* x; float* ws;     // ws [slices][c_out][ck + 1]
+};
+
+template <int WM, int WN, int TM, int TN>
+__global__ __launch_bounds__(CG_THREADS) void wgrad_kernel(WGrad c) {
+    static_assert(WM * WN * 64 == CG_THREADS, "four waves");
+    constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
+    constexpr int ROWS = CG_THREADS / WG_KT;                    // tile rows one pass of the 256 threads stages
+    constexpr int A_PER = BM / ROWS, B_PER = BN / ROWS;
+    constexpr int LDA = (BM % 64 == 0) ? BM + 33 : BM + 1;      // = 33 mod 64: the transposed stores of 32 lanes along rho hit 32
+    constexpr int LDB = (BN % 64 == 0) ? BN + 33 : BN + 1;      // banks, and lanes 32..63 read the next row 33 banks over
+    __shared__ float As[WG_KT * LDA];
+    __shared__ float Bs[WG_KT * LDB];
+
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int wm = wid / WN, wn = wid % WN;
+    const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
+    const int kr = tid % WG_KT, row0 = tid / WG_KT;             // this thread's reduction offset in a step, and its first row
+
+    // the columns this thread stages: x offset of tap (ci, j) inside an item, and the u s it needs at least
+    int xoff[B_PER], need[B_PER];
+    unsigned bias_col = 0;                                      // bit i: this thread's column i is db's
+#pragma unroll
+    for (int i = 0; i < B_PER; ++i) {
+        const int n = n0 + row0 + i * ROWS;
+        const bool tap = n < c.ck;                              // the bias column and columns past it read no x
+        const int ci = n / c.ksz, back = (c.ksz - 1 - (n - ci * c.ksz)) * c.dil;
+        xoff[i] = tap ? ci * c.t - back : 0;
+        need[i] = tap ? back : 0x7fffffff;
+        bias_col |= (n == c.ck && n < c.nc_live) ? 1u << i : 0u;
+    }
+
+    // Every load is unconditional, from a clamped address (element 0 of the item: a step exists only when the operands do), so
+    // that all of a step's loads are in flight while the step before it is multiplied; what is not an operand is masked, and
+    // the activation applied, when the registers are stored to LDS.
+    float ra[A_PER], rb[B_PER];
+    unsigned amask = 0, bmask = 0;
+    bool live = false;
+    auto load = [&](int step) {
+        const int rho = step * WG_KT + kr;
+        live = rho < c.red;
+        const int item = live ? rho / c.t_out : 0, u = live ? rho - item * c.t_out : 0;
+        const float* __restrict__ dyb = c.dy + (long long)item * c.c_out * c.t_out + u;
+        const float* __restrict__ xb = c.x + (long long)item * c.c_in * c.t;
+        const int p = u * c.stride;
+        amask = bmask = 0;
+#pragma unroll
+        for (int i = 0; i < A_PER; ++i) {
+            const int m = m0 + row0 + i * ROWS;
+            const bool ok = live && m < c.c_out;
+            ra[i] = dyb[ok ? (long long)m * c.t_out : 0];
+            amask |= ok ? 1u << i : 0u;
+        }
+#pragma unroll
+        for (int i = 0; i < B_PER; ++i) {
+            const bool ok = live && p >= need[i];
+            rb[i] = xb[ok ? xoff[i] + p : 0];
+            bmask |= ok ? 1u << i : 0u;
+        }
+    };
+    auto store = [&]() {
+#pragma unroll
+        for (int i = 0; i < A_PER; ++i) As[kr * LDA + row0 + i * ROWS] = (amask >> i & 1) ? ra[i] : 0.f;
+#pragma unroll
+        for (int i = 0; i < B_PER; ++i) {
+            const float one = (live && (bias_col >> i & 1)) ? 1.f : 0.f;
+            Bs[kr * LDB + row0 + i * ROWS] = (bmask >> i & 1) ? enc_act(rb[i], c.act, c.alpha) : one;
+        }
+    };
+
+    f32x16 acc[TM][TN];
+#pragma unroll
+    for (int a = 0; a < TM; ++a)
+#pragma unroll
+        for (int b = 0; b < TN; ++b)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+
+    const int n_steps = (c.red + WG_KT - 1) / WG_KT;
+    const int s0 = blockIdx.z * c.steps_per, s1 = min(n_steps, s0 + c.steps_per);
+    const int arow = wm * TM * 32 + (lane & 31), brow = wn * TN * 32 + (lane & 31), kh = lane >> 5;
+    if (s0 < s1) load(s0);
+    for (int st = s0; st < s1; ++st) {
+        store();
+        __syncthreads();
+        if (st + 1 < s1) load(st + 1);
+#pragma unroll
+        for (int kk = 0; kk < WG_KT; kk += 2) {
+            float av[TM], bv[TN];
+#pragma unroll
+            for (int a = 0; a < TM; ++a) av[a] = As[(kk + kh) * LDA + arow + a * 32];
+#pragma unroll
+            for (int b = 0; b < TN; ++b) bv[b] = Bs[(kk + kh) * LDB + brow + b * 32];
+#pragma unroll
+            for (int a = 0; a < TM; ++a)
+#pragma unroll
+                for (int b = 0; b < TN; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[a], bv[b], acc[a][b], 0, 0, 0);
+        }
+        __syncthreads();
+    }
+
+    // C/D map col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5); the partial tile goes to ws[slice][m][n]
+    const int nc = c.ck + 1;
+    float* __restrict__ wsz = c.ws + (size_t)blockIdx.z * c.c_out * nc;
+#pragma unroll
+    for (int b = 0; b < TN; ++b) {
+        const int n = n0 + wn * TN * 32 + b * 32 + (lane & 31);
+        if (n >= c.nc_live) continue;
+#pragma unroll
+        for (int a = 0; a < TM; ++a)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int m = m0 + wm * TM * 32 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                if (m < c.c_out) wsz[(size_t)m * nc + n] = acc[a][b][r];
+            }
+    }
+}
+
+__global__ __launch_bounds__(CG_THREADS) void wgrad_fold_kernel(const float* __restrict__ ws, float* __restrict__ dw,
+                                                                float* __restrict__ db, int c_out, int ck, int slices) {
+    const int nc = ck + 1, nc_live = db ? nc : ck;
+    const long long o = (long long)blockIdx.x * CG_THREADS + threadIdx.x;
+    if (o >= (long long)c_out * nc_live) return;
+    const int m = (int)(o / nc_live), n = (int)(o - (long long)m * nc_live);
+    const size_t total = (size_t)c_out * nc;
+    const float* __restrict__ p = ws + (size_t)m * nc + n;
+    double s = 0.0;
+    int z = 0;
+    for (; z + 8 <= slices; z += 8) {                           // eight loads in flight, added in ascending order
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = p[(size_t)(z + j) * total];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) s += (double)v[j];
+    }
+    for (; z < slices; ++z) s += (double)p[(size_t)z * total];
+    if (n < ck) dw[(size_t)m * ck + n] = (float)s;
+    else db[m] = (float)s;
+}
+
+// ---- host ----
+static int enc_down_geometry(const std::string& f, int n_items, int c_in, int t, int c_out, int kernel, int stride, int& t_out) {
+    if (n_items < 0 || c_in <= 0 || t <= 0 || c_out <= 0 || kernel <= 0 || stride <= 0)
+        return fail(ADK_ERR_ARG, f + ": need n_items >= 0, c_in, t, c_out, kernel, stride > 0");
+    if ((long long)kernel != 2LL * stride) return fail(ADK_ERR_ARG, f + ": kernel must be 2 * stride");
+    t_out = (t - 1) / stride + 1;
+    const long long n_cols = (long long)n_items * t_out;
+    if (t >= (1 << 30) || stride > 65535 || (long long)c_in * kernel >= (1LL << 30) || (long long)c_out * kernel >= (1LL << 30) ||
+        (n_cols + 31) / 32 >= (1LL << 31) || (c_in + 31) / 32 > 65535 || (c_out + 31) / 32 > 65535)
+        return fail(ADK_ERR_ARG, f + ": layer too large");
+    return ADK_OK;
+}
+
+// The tile follows M as DEC_LAUNCH's: 128 x 128 from M >= 128, 64 x 128 from M >= 64, else 32 x 128; z = phases.
+#define ENC_LAUNCH(kernel, c, m, phases, s)                                                                              \
+    do {                                                                                                                 \
+        const unsigned nx128 = (unsigned)(((c).n_cols + 127) / 128);                                                      \
+        if ((m) >= 128) hipLaunchKernelGGL((kernel<2, 2, 2, 2>), dim3(nx128, ((m) + 127) / 128, phases), dim3(CG_THREADS), 0, s, c); \
+        else if ((m) >= 64) hipLaunchKernelGGL((kernel<2, 2, 1, 2>), dim3(nx128, ((m) + 63) / 64, phases), dim3(CG_THREADS), 0, s, c); \
+        else hipLaunchKernelGGL((kernel<1, 4, 1, 1>), dim3(nx128, ((m) + 31) / 32, phases), dim3(CG_THREADS), 0, s, c);  \
+    } while (0)
+
+// The weight gradient's checks, geometry and slice rule.  S is a function of the shape only: with `tiles` output tiles and
+// n_steps 32-deep steps, S0 = min(ceil(512 / tiles), max(1, n_steps / 4)), a slice is ceil(n_steps / S0) steps and S the slices
+// that many steps make (so no slice is empty; the last one may be short).
+static int wgrad_plan(const std::string& f, int n_items, int c_in, int t, int c_out, int kernel, int dil, int stride, int act,
+                      float alpha, WGrad& g, long long& ws_bytes) {
+    if (n_items < 0 || c_in <= 0 || t <= 0 || c_out <= 0 || kernel <= 0 || dil <= 0 || stride <= 0)
+        return fail(ADK_ERR_ARG, f + ": need n_items >= 0, c_in, t, c_out, kernel, dilation, stride > 0");
+    if (act != ENC_ACT_NONE && act != ENC_ACT_ELU) return fail(ADK_ERR_ARG, f + ": act must be 0 (none) or 1 (ELU)");
+    if (act == ENC_ACT_ELU && !(alpha == alpha)) return fail(ADK_ERR_ARG, f + ": alpha is NaN");
+    const int t_out = (t - 1) / stride + 1;
+    const long long red = (long long)n_items * t_out, ck = (long long)c_in * kernel;
+    if (t >= (1 << 30) || (long long)(kernel - 1) * dil >= (1LL << 30) || ck >= (1LL << 30) || (long long)c_in * t >= (1LL << 31) ||
+        red >= (1LL << 31) - WG_KT || (long long)c_out * (ck + 1) >= (1LL << 31) || (c_out + 31) / 32 > 65535)
+        return fail(ADK_ERR_ARG, f + ": layer too large");
+    const int bm = c_out >= 128 ? 128 : c_out >= 64 ? 64 : 32;
+    const long long tiles = (long long)((c_out + bm - 1) / bm) * ((ck + 1 + 127) / 128);
+    const long long n_steps = (red + WG_KT - 1) / WG_KT;
+    const long long want = std::max<long long>(1, (WG_TARGET_WGS + tiles - 1) / tiles);
+    const long long s0 = std::max<long long>(1, std::min<long long>(want, n_steps / WG_MIN_STEPS));
+    const long long steps_per = std::max<long long>(1, (n_steps + s0 - 1) / s0);
+    const long long slices = std::max<long long>(1, (n_steps + steps_per - 1) / steps_per);
+    g.n_items = n_items; g.c_in = c_in; g.c_out = c_out; g.t = t; g.t_out = t_out; g.ksz = kernel; g.dil = dil; g.stride = stride;
+    g.act = act; g.alpha = alpha; g.ck = (int)ck; g.nc_live = (int)ck + 1; g.red = (int)red; g.steps_per = (int)steps_per; g.slices = (int)slices;
+    ws_bytes = slices * c_out * (ck + 1) * 4;
+    return ADK_OK;
+}
+
+}  // namespace adk
+
+using namespace adk;
+
+extern "C" int adk_enc_down(const float* x, const float* w, const float* bias, float* y, int32_t n_items, int32_t c_in, int32_t t,
+                            int32_t c_out, int32_t kernel, int32_t stride, void* stream) {
+    const std::string f = "adk_enc_down";
+    EncDown c;
+    int rc = enc_down_geometry(f, n_items, c_in, t, c_out, kernel, stride, c.t_out);
+    if (rc != ADK_OK) return rc;
+    rc = check_pointers(f, "x/w/bias/y", n_items > 0 && (!x || !w || !y), {x, w, bias, y});
+    if (rc != ADK_OK) return rc;
+    if (n_items == 0) return ADK_OK;
+    c.n_items = n_items; c.c_in = c_in; c.c_out = c_out; c.t = t; c.ksz = kernel; c.stride = stride;
+    c.n_cols = (long long)n_items * c.t_out;
+    c.x = x; c.w = w; c.bias = bias; c.y = y;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DeviceGuard guard(device_of(y));
+    ENC_LAUNCH(enc_down_kernel, c, c_out, 1, s);
+    ADK_HIP_CHECK(hipGetLastError());
+    return ADK_OK;
+}
+
+extern "C" int adk_enc_down_grad(const float* dy, const float* w, float* dx, int32_t n_items, int32_t c_in, int32_t t, int32_t c_out,
+                                 int32_t kernel, int32_t stride, void* stream) {
+    const std::string f = "adk_enc_down_grad";
+    EncDownGrad c;
+    int rc = enc_down_geometry(f, n_items, c_in, t, c_out, kernel, stride, c.t_out);
+    if (rc != ADK_OK) return rc;
+    rc = check_pointers(f, "dy/w/dx", n_items > 0 && (!dy || !w || !dx), {dy, w, dx});
+    if (rc != ADK_OK) return rc;
+    if (n_items == 0) return ADK_OK;
+    c.n_items = n_items; c.c_in = c_in; c.c_out = c_out; c.t = t; c.ksz = kernel; c.stride = stride;
+    c.n_cols = (long long)n_items * c.t_out;                   // phase 0 has the most columns, t_out per item: the grid's x
+    c.dy = dy; c.w = w; c.dx = dx;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DeviceGuard guard(device_of(dx));
+    ENC_LAUNCH(enc_down_grad_kernel, c, c_in, stride, s);
+    ADK_HIP_CHECK(hipGetLastError());
+    return ADK_OK;
+}
+
+extern "C" int adk_conv_wgrad_plan(int32_t n_items, int32_t c_in, int32_t t, int32_t c_out, int32_t kernel, int32_t dilation,
+                                   int32_t stride, int64_t* workspace_bytes, int32_t* slices) {
+    WGrad g;
+    long long bytes = 0;
+    const int rc = wgrad_plan("adk_conv_wgrad_plan", n_items, c_in, t, c_out, kernel, dilation, stride, ENC_ACT_NONE, 0.f, g, bytes);
+    if (rc != ADK_OK) return rc;
+    if (workspace_bytes) *workspace_bytes = bytes;
+    if (slices) *slices = g.slices;
+    return ADK_OK;
+}
+
+extern "C" int adk_conv_wgrad(const float* dy, const float* x, float* dw, float* db, void* workspace, int32_t n_items, int32_t c_in,
+                              int32_t t, int32_t c_out, int32_t kernel, int32_t dilation, int32_t stride, int32_t act, float alpha,
+                              void* stream) {
+    const std::string f = "adk_conv_wgrad";
+    WGrad c;
+    long long bytes = 0;
+    int rc = wgrad_plan(f, n_items, c_in, t, c_out, kernel, dilation, stride, act, alpha, c, bytes);
+    if (rc != ADK_OK) return rc;
+    rc = check_pointers(f, "dy/x/dw/db/workspace", !dw || !workspace || (n_items > 0 && (!dy || !x)), {dy, x, dw, db, workspace});
+    if (rc != ADK_OK) return rc;
+    c.dy = dy; c.x = x; c.ws = static_cast<float*>(workspace);
+    c.nc_live = db ? c.ck + 1 : c.ck;                          // without db its column is not computed
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DeviceGuard guard(device_of(dw));
+    const int nc = c.nc_live;
+    const unsigned nx = (unsigned)((nc + 127) / 128);
+    if (c_out >= 128) hipLaunchKernelGGL((wgrad_kernel<2, 2, 2, 2>), dim3(nx, (c_out + 127) / 128, c.slices), dim3(CG_THREADS), 0, s, c);
+    else if (c_out >= 64) hipLaunchKernelGGL((wgrad_kernel<2, 2, 1, 2>), dim3(nx, (c_out + 63) / 64, c.slices), dim3(CG_THREADS), 0, s, c);
+    else hipLaunchKernelGGL((wgrad_kernel<1, 4, 1, 1>), dim3(nx, (c_out + 31) / 32, c.slices), dim3(CG_THREADS), 0, s, c);
+    ADK_HIP_CHECK(hipGetLastError());
+    const long long total = (long long)c_out * nc;
+    hipLaunchKernelGGL(wgrad_fold_kernel, dim3((unsigned)((total + CG_THREADS - 1) / CG_THREADS)), dim3(CG_THREADS), 0, s, c.ws, dw, db,
+                       (int)c_out, c.ck, c.slices);
+    ADK_HIP_CHECK(hipGetLastError());
+    return ADK_OK;
+}

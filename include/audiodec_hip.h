@@ -475,6 +475,45 @@ int adk_rvq_st_grad(const float* dzq, const float* up_vq, const float* z, const 
                     int32_t n_items, int32_t dim, int32_t t, int32_t size, void* stream);
 
 /*
+ * The encoder's training half (models/autoencoder/modules/encoder.py:25-134, 'causal' mode): the strided down-sampling conv,
+ * forward and backward to its input, and the gradient of a causal conv with respect to its weight and bias.  The stride-1 layers'
+ * forward and backward to the input are adk_dec_conv / adk_dec_conv_grad.  Exact f32 as the adk_dec_* calls, no atomics, every
+ * split of a sum a function of the shape alone: bitwise reproducible.  a, act and alpha as above.
+ * With t the input length, t_out = (t - 1) / stride + 1; terms with an index outside [0, t) or [0, t_out) are zero.
+ * adk_enc_down: CausalConv1d.forward (layers/conv_layer.py:146-149) for kernel == 2 stride, dilation 1, no input activation
+ *   (EncoderBlock.conv):  x [n_items][c_in][t] -> y [n_items][c_out][t_out]
+ *   y[b][o][u] = bias[o] + sum_{ci, j < kernel} W[o][ci][j] x[b][ci][u stride - (kernel-1-j)]
+ *   w is [c_in * kernel][c_out] (adk_dec_conv's gemm layout); bias may be NULL.
+ * adk_enc_down_grad: its backward to x, given dy of y's shape:
+ *   dx[b][ci][v] = sum_o sum_{j : (v + kernel-1-j) % stride == 0} W[o][ci][j] dy[b][o][(v + kernel-1-j) / stride]
+ *   One GEMM per phase r = v % stride, whose two taps are j0 = (r + stride - 1) % stride (reading u0 = v / stride + (r ? 2 : 1))
+ *   and j0 + stride (reading u0 - 1).  w is [r < stride][(o, tap) at 2 o + tap][c_in], tap 0 = W[o][ci][j0], tap 1 =
+ *   W[o][ci][j0 + stride].  dx is fully written.
+ * adk_conv_wgrad: the weight and bias gradient of a causal conv of any kernel, dilation and stride, given dy [n_items][c_out][t_out]
+ *   and the conv's input x [n_items][c_in][t], which is read through a:
+ *   dw[o][ci][j] = sum_{b,u} dy[b][o][u] a(x[b][ci][u stride - (kernel-1-j) dilation])     dw [c_out][c_in][kernel], the reference's
+ *   db[o]        = sum_{b,u} dy[b][o][u]                                                   db [c_out] or NULL
+ *   A GEMM whose reduction (b, u) is cut into S slices of whole 32-term steps; every (tile, slice) writes an f32 partial into
+ *   `workspace`, and a second launch adds a weight's S partials in ascending order in f64 and rounds once.  dw and db are fully
+ *   written (zeros for n_items == 0); with db NULL the GEMM's last column is not computed.  workspace: adk_conv_wgrad_plan's
+ *   bytes, 4-byte aligned, any contents.
+ * adk_conv_wgrad_plan: host only, no HIP call: *workspace_bytes = 4 S c_out (c_in kernel + 1) and *slices = S (either may be
+ *   NULL) for a shape.  S depends on the shape alone: with tiles = ceil(c_out / BM) ceil((c_in kernel + 1) / 128), BM = 128 / 64 /
+ *   32 from c_out >= 128 / >= 64 / below, and n = ceil(n_items t_out / 32) steps: S0 = max(1, min(ceil(512 / tiles), n / 4)), a
+ *   slice has ceil(n / S0) steps and S = ceil(n / that), at least 1.
+ * n_items == 0 is a no-op of the first two calls.  Every argument is checked before any HIP call (ADK_ERR_ARG).  No allocation, no
+ * synchronisation.
+ */
+int adk_enc_down(const float* x, const float* w, const float* bias, float* y, int32_t n_items, int32_t c_in, int32_t t,
+                 int32_t c_out, int32_t kernel, int32_t stride, void* stream);
+int adk_enc_down_grad(const float* dy, const float* w, float* dx, int32_t n_items, int32_t c_in, int32_t t, int32_t c_out,
+                      int32_t kernel, int32_t stride, void* stream);
+int adk_conv_wgrad_plan(int32_t n_items, int32_t c_in, int32_t t, int32_t c_out, int32_t kernel, int32_t dilation, int32_t stride,
+                        int64_t* workspace_bytes, int32_t* slices);
+int adk_conv_wgrad(const float* dy, const float* x, float* dw, float* db, void* workspace, int32_t n_items, int32_t c_in, int32_t t,
+                   int32_t c_out, int32_t kernel, int32_t dilation, int32_t stride, int32_t act, float alpha, void* stream);
+
+/*
  * Multi-resolution STFT loss and waveform-shape loss, one resolution / one window length per call (losses/stft_loss.py:19-170,
  * losses/waveform_loss.py:15-75).  The STFT is adk_logmel's: torch.stft's defaults, the window [win_length] centred in n_fft,
  * 1 + n_samples/hop frames, n_fft/2 + 1 bins, mag = sqrt(max(re^2 + im^2, eps)) (a NaN stays NaN).
