@@ -22,16 +22,13 @@
 //                          transposed to the MFMA's [rho][m] / [rho][n].  The reduction is cut into S slices of whole 32-deep
 //                          steps (wgrad_plan: a function of the shape only); workgroup (tile, slice) writes its f32 partial tile
 //                          to the workspace [slice][m][n].
-//   wgrad_fold_kernel:     one thread per (m, n): the S partials in ascending slice order in f64, rounded once, stored as
-//                          dW [co][ci][k] (the reference's layout: m (C_in k) + n) or db[m].
-#include "conv_gemm_f32.h"
+//   wgrad_fold_kernel:     (wgrad_fold.h, shared with dec_wgrad.hip) one thread per (m, n): the S partials in ascending slice
+//                          order in f64, rounded once, stored as dW [co][ci][k] (the reference's layout: m (C_in k) + n) or db[m].
+#include "wgrad_fold.h"
 
 namespace adk {
 
 constexpr int ENC_ACT_NONE = 0, ENC_ACT_ELU = 1;
-constexpr int WG_KT = 32;                           // reduction depth of one LDS slice of the weight gradient
-constexpr int WG_TARGET_WGS = 512;                  // workgroups a weight-gradient launch aims at (two per CU of 256)
-constexpr int WG_MIN_STEPS = 4;                     // a slice is at least this many 32-deep steps (when there are that many)
 
 // dec_grad.hip's dec_act, restated (that file's code objects stay as they are)
 __device__ __forceinline__ float enc_act(float v, int act, float alpha) {
@@ -252,28 +249,6 @@ __global__ __launch_bounds__(CG_THREADS) void wgrad_kernel(WGrad c) {
     }
 }
 
-__global__ __launch_bounds__(CG_THREADS) void wgrad_fold_kernel(const float* __restrict__ ws, float* __restrict__ dw,
-                                                                float* __restrict__ db, int c_out, int ck, int slices) {
-    const int nc = ck + 1, nc_live = db ? nc : ck;
-    const long long o = (long long)blockIdx.x * CG_THREADS + threadIdx.x;
-    if (o >= (long long)c_out * nc_live) return;
-    const int m = (int)(o / nc_live), n = (int)(o - (long long)m * nc_live);
-    const size_t total = (size_t)c_out * nc;
-    const float* __restrict__ p = ws + (size_t)m * nc + n;
-    double s = 0.0;
-    int z = 0;
-    for (; z + 8 <= slices; z += 8) {                           // eight loads in flight, added in ascending order
-        float v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = p[(size_t)(z + j) * total];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) s += (double)v[j];
-    }
-    for (; z < slices; ++z) s += (double)p[(size_t)z * total];
-    if (n < ck) dw[(size_t)m * ck + n] = (float)s;
-    else db[m] = (float)s;
-}
-
 // ---- host ----
 static int enc_down_geometry(const std::string& f, int n_items, int c_in, int t, int c_out, int kernel, int stride, int& t_out) {
     if (n_items < 0 || c_in <= 0 || t <= 0 || c_out <= 0 || kernel <= 0 || stride <= 0)
@@ -296,9 +271,7 @@ static int enc_down_geometry(const std::string& f, int n_items, int c_in, int t,
         else hipLaunchKernelGGL((kernel<1, 4, 1, 1>), dim3(nx128, ((m) + 31) / 32, phases), dim3(CG_THREADS), 0, s, c);  \
     } while (0)
 
-// The weight gradient's checks, geometry and slice rule.  S is a function of the shape only: with `tiles` output tiles and
-// n_steps 32-deep steps, S0 = min(ceil(512 / tiles), max(1, n_steps / 4)), a slice is ceil(n_steps / S0) steps and S the slices
-// that many steps make (so no slice is empty; the last one may be short).
+// The weight gradient's checks and geometry; the slice rule is wgrad_fold.h's wgrad_slices.
 static int wgrad_plan(const std::string& f, int n_items, int c_in, int t, int c_out, int kernel, int dil, int stride, int act,
                       float alpha, WGrad& g, long long& ws_bytes) {
     if (n_items < 0 || c_in <= 0 || t <= 0 || c_out <= 0 || kernel <= 0 || dil <= 0 || stride <= 0)
@@ -313,10 +286,8 @@ static int wgrad_plan(const std::string& f, int n_items, int c_in, int t, int c_
     const int bm = c_out >= 128 ? 128 : c_out >= 64 ? 64 : 32;
     const long long tiles = (long long)((c_out + bm - 1) / bm) * ((ck + 1 + 127) / 128);
     const long long n_steps = (red + WG_KT - 1) / WG_KT;
-    const long long want = std::max<long long>(1, (WG_TARGET_WGS + tiles - 1) / tiles);
-    const long long s0 = std::max<long long>(1, std::min<long long>(want, n_steps / WG_MIN_STEPS));
-    const long long steps_per = std::max<long long>(1, (n_steps + s0 - 1) / s0);
-    const long long slices = std::max<long long>(1, (n_steps + steps_per - 1) / steps_per);
+    long long steps_per = 1, slices = 1;
+    wgrad_slices(tiles, n_steps, steps_per, slices);
     g.n_items = n_items; g.c_in = c_in; g.c_out = c_out; g.t = t; g.t_out = t_out; g.ksz = kernel; g.dil = dil; g.stride = stride;
     g.act = act; g.alpha = alpha; g.ck = (int)ck; g.nc_live = (int)ck + 1; g.red = (int)red; g.steps_per = (int)steps_per; g.slices = (int)slices;
     ws_bytes = slices * c_out * (ck + 1) * 4;
@@ -396,9 +367,7 @@ extern "C" int adk_conv_wgrad(const float* dy, const float* x, float* dw, float*
     else if (c_out >= 64) hipLaunchKernelGGL((wgrad_kernel<2, 2, 1, 2>), dim3(nx, (c_out + 63) / 64, c.slices), dim3(CG_THREADS), 0, s, c);
     else hipLaunchKernelGGL((wgrad_kernel<1, 4, 1, 1>), dim3(nx, (c_out + 31) / 32, c.slices), dim3(CG_THREADS), 0, s, c);
     ADK_HIP_CHECK(hipGetLastError());
-    const long long total = (long long)c_out * nc;
-    hipLaunchKernelGGL(wgrad_fold_kernel, dim3((unsigned)((total + CG_THREADS - 1) / CG_THREADS)), dim3(CG_THREADS), 0, s, c.ws, dw, db,
-                       (int)c_out, c.ck, c.slices);
+    launch_wgrad_fold(c.ws, dw, db, (int)c_out, c.ck, c.slices, s);
     ADK_HIP_CHECK(hipGetLastError());
     return ADK_OK;
 }

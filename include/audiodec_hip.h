@@ -514,6 +514,31 @@ int adk_conv_wgrad(const float* dy, const float* x, float* dw, float* db, void* 
                    int32_t c_out, int32_t kernel, int32_t dilation, int32_t stride, int32_t act, float alpha, void* stream);
 
 /*
+ * The decoder's training half: the weight and bias gradient of CausalConvTranspose1d (layers/conv_layer.py:189-192) for
+ * kernel == 2 stride, the layer adk_dec_convtr computes; the decoder's stride-1 convs go through adk_conv_wgrad.  Exact f32, no
+ * atomics, every split of a sum a function of the shape alone: bitwise reproducible.  a, act and alpha as above.
+ * adk_convtr_wgrad: given dy [n_items][c_out][t stride] and the layer's input x [n_items][c_in][t], which is read through a:
+ *   dw[ci][o][q] = sum_{b,i} a(x[b][ci][i]) g(b, o, i, q),  q < 2 stride                     dw [c_in][c_out][kernel], the reference's
+ *   g            = [i stride + q < t stride] dy[b][o][i stride + q] + [i == 0 and q >= stride] dy[b][o][q - stride]
+ *   db[o]        = sum_{b,u} dy[b][o][u]                                                     db [c_out] or NULL
+ *   One GEMM, M = c_in, N = 2 c_out stride, whose reduction (b, i) is cut into S slices of whole 32-term steps; every (tile,
+ *   slice) writes an f32 partial into `workspace`, and adk_conv_wgrad's fold adds a weight's S partials in ascending order in f64
+ *   and rounds once.  db, when asked for, is a sum of its own: per channel, f64 partials of fixed chunks of (b, u), added in
+ *   ascending order and rounded once.  dw and db are fully written (zeros for n_items == 0).  workspace:
+ *   adk_convtr_wgrad_plan's bytes, 8-byte aligned, any contents.
+ * adk_convtr_wgrad_plan: host only, no HIP call: *workspace_bytes and *slices = S (either may be NULL) for a shape.  S is
+ *   adk_conv_wgrad_plan's rule with tiles = ceil(c_in / BM) ceil(2 c_out stride / 128), BM = 128 / 64 / 32 from c_in >= 128 / >= 64 /
+ *   below, and n = ceil(n_items t / 32) steps.  The bytes are 4 S c_in (2 c_out stride + 1), rounded up to 8, plus 8 c_out C for
+ *   db's C = ceil(L / ceil(L / min(64, ceil(L / 4096)))) chunks of L = n_items t stride terms (C = 1 for L = 0).
+ * Every argument is checked before any HIP call (ADK_ERR_ARG); a stride above 18 is refused as too large.  No allocation, no
+ * synchronisation.
+ */
+int adk_convtr_wgrad_plan(int32_t n_items, int32_t c_in, int32_t t, int32_t c_out, int32_t kernel, int32_t stride,
+                          int64_t* workspace_bytes, int32_t* slices);
+int adk_convtr_wgrad(const float* dy, const float* x, float* dw, float* db, void* workspace, int32_t n_items, int32_t c_in, int32_t t,
+                     int32_t c_out, int32_t kernel, int32_t stride, int32_t act, float alpha, void* stream);
+
+/*
  * Multi-resolution STFT loss and waveform-shape loss, one resolution / one window length per call (losses/stft_loss.py:19-170,
  * losses/waveform_loss.py:15-75).  The STFT is adk_logmel's: torch.stft's defaults, the window [win_length] centred in n_fft,
  * 1 + n_samples/hop frames, n_fft/2 + 1 bins, mag = sqrt(max(re^2 + im^2, eps)) (a NaN stays NaN).
