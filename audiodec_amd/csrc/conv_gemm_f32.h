@@ -32,6 +32,18 @@ __device__ __forceinline__ float cg_act(float v, int act, float slope) {
     return (act == CG_ACT_LEAKY && v < 0.f) ? v * slope : v;
 }
 
+// A conv's INPUT activation in the training kernels (dec_grad.hip, enc_grad.hip, dec_wgrad.hip) and its derivative: none,
+// ELU(alpha) (the inference kernels' ELU for alpha = 1) or LeakyReLU(alpha), whose derivative at 0 is the slope, as torch's is.
+constexpr int IN_ACT_NONE = 0, IN_ACT_ELU = 1, IN_ACT_LEAKY = 2;
+__device__ __forceinline__ float in_act(float v, int act, float alpha) {
+    if (act == IN_ACT_NONE || v > 0.f) return v;
+    return act == IN_ACT_ELU ? alpha * expm1_neg(v) : alpha * v;
+}
+__device__ __forceinline__ float in_dact(float v, int act, float alpha) {
+    if (act == IN_ACT_NONE || v > 0.f) return 1.f;
+    return act == IN_ACT_ELU ? alpha * (expm1_neg(v) + 1.f) : alpha;
+}
+
 // The pointers of a conv's argument struct, which is one of these and the family's geometry.
 struct CgForwardPtrs {
     const float* x;

@@ -3,7 +3,8 @@
 // v_mfma_f32_32x32x2_f32; every partial is written once by one accumulator, nothing is added atomically, and every split of a sum
 // is a function of the shape alone: the gradients are bitwise reproducible.
 //
-// a is the conv's INPUT activation as in dec_grad.hip, none or ELU(alpha).  s stride, T the input length, T s the output's.  The
+// a is the conv's INPUT activation as in dec_grad.hip (conv_gemm_f32.h's in_act): none, ELU(alpha) or, for adk_voc_convtr_wgrad
+// (the HiFi-GAN vocoder's upsampling layers), LeakyReLU(alpha).  s stride, T the input length, T s the output's.  The
 // forward (dec_grad.hip's dec_convtr_kernel) is
 //   y[b][co][i s + r] = bias[co] + sum_ci W[ci][co][r] a(x[b][ci][i]) + W[ci][co][s + r] a(x[b][ci][max(i-1, 0)])
 // so, with q in [0, 2s):
@@ -32,16 +33,10 @@
 
 namespace adk {
 
-constexpr int DW_ACT_NONE = 0, DW_ACT_ELU = 1;
 constexpr int DW_BN = 128;                          // columns of a tile, whatever its rows
 constexpr int DW_RUN = WG_KT + 1;                   // frames of dy a step reads per channel: its 32 rows' and the one after
 constexpr int DW_B_PER = 12;                        // dy elements a thread stages per step, at most (a stride up to 18 fits)
 constexpr int DW_BIAS_CHUNK = 4096, DW_BIAS_MAX_CHUNKS = 64;
-
-// dec_grad.hip's dec_act, restated (that file's code objects stay as they are)
-__device__ __forceinline__ float dw_act(float v, int act, float alpha) {
-    return (act == DW_ACT_ELU && !(v > 0.f)) ? alpha * expm1_neg(v) : v;
-}
 
 struct ConvTrWGrad {
     int n_items, c_in, c_out, t, stride, act;
@@ -135,7 +130,7 @@ __global__ __launch_bounds__(CG_THREADS) void convtr_wgrad_kernel(ConvTrWGrad c)
     };
     auto store = [&]() {
 #pragma unroll
-        for (int a = 0; a < A_PER; ++a) As[kr * LDA + row0 + a * ROWS] = (amask >> a & 1) ? dw_act(ra[a], c.act, c.alpha) : 0.f;
+        for (int a = 0; a < A_PER; ++a) As[kr * LDA + row0 + a * ROWS] = (amask >> a & 1) ? in_act(ra[a], c.act, c.alpha) : 0.f;
 #pragma unroll
         for (int i = 0; i < DW_B_PER; ++i) {
             if (tap1 >> i & 1) Bs[fr_[i] * LDB + col[i]] = (own >> i & 1) ? rb[i] : 0.f;
@@ -220,12 +215,13 @@ __global__ __launch_bounds__(RED_THREADS) void convtr_bias_fold_kernel(const dou
 }
 
 // The checks, geometry, slice rule and workspace of the transposed conv's weight gradient.
-static int convtr_wgrad_plan(const std::string& f, int n_items, int c_in, int t, int c_out, int kernel, int stride, int act, float alpha,
-                             ConvTrWGrad& g, long long& ws_floats, long long& ws_bytes) {
+static int convtr_wgrad_plan(const std::string& f, int n_items, int c_in, int t, int c_out, int kernel, int stride, int act, int max_act,
+                             float alpha, ConvTrWGrad& g, long long& ws_floats, long long& ws_bytes) {
     if (n_items < 0 || c_in <= 0 || t <= 0 || c_out <= 0 || kernel <= 0 || stride <= 0)
         return fail(ADK_ERR_ARG, f + ": need n_items >= 0, c_in, t, c_out, kernel, stride > 0");
-    if (act != DW_ACT_NONE && act != DW_ACT_ELU) return fail(ADK_ERR_ARG, f + ": act must be 0 (none) or 1 (ELU)");
-    if (act == DW_ACT_ELU && !(alpha == alpha)) return fail(ADK_ERR_ARG, f + ": alpha is NaN");
+    if (act < IN_ACT_NONE || act > max_act)
+        return fail(ADK_ERR_ARG, f + (max_act == IN_ACT_ELU ? ": act must be 0 (none) or 1 (ELU)" : ": act must be 0 (none), 1 (ELU) or 2 (LeakyReLU)"));
+    if (act != IN_ACT_NONE && !(alpha == alpha)) return fail(ADK_ERR_ARG, f + ": alpha is NaN");
     const long long ts = (long long)t * stride, nn = 2LL * c_out * stride, red = (long long)n_items * t;
     // a tile's columns touch at most (BN - 1) / 2s + 2 channels, each with 33 s elements a step: they must fit the staging registers
     const long long el = stride <= DW_BN ? ((DW_BN - 1) / (2LL * stride) + 2) * DW_RUN * stride : (1LL << 40);
@@ -250,27 +246,12 @@ static int convtr_wgrad_plan(const std::string& f, int n_items, int c_in, int t,
     return ADK_OK;
 }
 
-}  // namespace adk
-
-using namespace adk;
-
-extern "C" int adk_convtr_wgrad_plan(int32_t n_items, int32_t c_in, int32_t t, int32_t c_out, int32_t kernel, int32_t stride,
-                                     int64_t* workspace_bytes, int32_t* slices) {
-    ConvTrWGrad g;
-    long long floats = 0, bytes = 0;
-    const int rc = convtr_wgrad_plan("adk_convtr_wgrad_plan", n_items, c_in, t, c_out, kernel, stride, DW_ACT_NONE, 0.f, g, floats, bytes);
-    if (rc != ADK_OK) return rc;
-    if (workspace_bytes) *workspace_bytes = bytes;
-    if (slices) *slices = g.slices;
-    return ADK_OK;
-}
-
-extern "C" int adk_convtr_wgrad(const float* dy, const float* x, float* dw, float* db, void* workspace, int32_t n_items, int32_t c_in,
-                                int32_t t, int32_t c_out, int32_t kernel, int32_t stride, int32_t act, float alpha, void* stream) {
-    const std::string f = "adk_convtr_wgrad";
+// adk_convtr_wgrad (max_act IN_ACT_ELU) and adk_voc_convtr_wgrad (IN_ACT_LEAKY)
+static int convtr_wgrad(const std::string& f, int max_act, const float* dy, const float* x, float* dw, float* db, void* workspace,
+                        int n_items, int c_in, int t, int c_out, int kernel, int stride, int act, float alpha, void* stream) {
     ConvTrWGrad c;
     long long floats = 0, bytes = 0;
-    int rc = convtr_wgrad_plan(f, n_items, c_in, t, c_out, kernel, stride, act, alpha, c, floats, bytes);
+    int rc = convtr_wgrad_plan(f, n_items, c_in, t, c_out, kernel, stride, act, max_act, alpha, c, floats, bytes);
     if (rc != ADK_OK) return rc;
     rc = check_pointers(f, "dy/x/dw/db/workspace", !dw || !workspace || (n_items > 0 && (!dy || !x)), {dy, x, dw, db, workspace});
     if (rc != ADK_OK) return rc;
@@ -295,4 +276,31 @@ extern "C" int adk_convtr_wgrad(const float* dy, const float* x, float* dw, floa
         ADK_HIP_CHECK(hipGetLastError());
     }
     return ADK_OK;
+}
+
+}  // namespace adk
+
+using namespace adk;
+
+extern "C" int adk_convtr_wgrad_plan(int32_t n_items, int32_t c_in, int32_t t, int32_t c_out, int32_t kernel, int32_t stride,
+                                     int64_t* workspace_bytes, int32_t* slices) {
+    ConvTrWGrad g;
+    long long floats = 0, bytes = 0;
+    const int rc = convtr_wgrad_plan("adk_convtr_wgrad_plan", n_items, c_in, t, c_out, kernel, stride, IN_ACT_NONE, IN_ACT_NONE, 0.f, g,
+                                     floats, bytes);
+    if (rc != ADK_OK) return rc;
+    if (workspace_bytes) *workspace_bytes = bytes;
+    if (slices) *slices = g.slices;
+    return ADK_OK;
+}
+
+extern "C" int adk_convtr_wgrad(const float* dy, const float* x, float* dw, float* db, void* workspace, int32_t n_items, int32_t c_in,
+                                int32_t t, int32_t c_out, int32_t kernel, int32_t stride, int32_t act, float alpha, void* stream) {
+    return convtr_wgrad("adk_convtr_wgrad", IN_ACT_ELU, dy, x, dw, db, workspace, n_items, c_in, t, c_out, kernel, stride, act, alpha, stream);
+}
+extern "C" int adk_voc_convtr_wgrad(const float* dy, const float* x, float* dw, float* db, void* workspace, int32_t n_items,
+                                    int32_t c_in, int32_t t, int32_t c_out, int32_t kernel, int32_t stride, int32_t act, float alpha,
+                                    void* stream) {
+    return convtr_wgrad("adk_voc_convtr_wgrad", IN_ACT_LEAKY, dy, x, dw, db, workspace, n_items, c_in, t, c_out, kernel, stride, act, alpha,
+                        stream);
 }

@@ -3,7 +3,8 @@
 // Exact f32 on v_mfma_f32_32x32x2_f32; every output element is written once by one thread or one accumulator, nothing is added
 // atomically, and every split of a sum is a function of the shape alone: forward and gradients are bitwise reproducible.
 //
-// a is a conv's INPUT activation as in dec_grad.hip, none or ELU(alpha): a(x) = x > 0 ? x : alpha expm1_neg(x).
+// a is a conv's INPUT activation as in dec_grad.hip (conv_gemm_f32.h's in_act): none, ELU(alpha) or LeakyReLU(alpha).  adk_conv_wgrad
+// (encoder and symmetric decoder) takes none or ELU and one group, adk_voc_conv_wgrad (the HiFi-GAN vocoder) all three and G groups.
 // k kernel, d dilation, s stride, T the input length, T_out = (T - 1) / s + 1; an index outside [0, T) or [0, T_out) is skipped
 // (the causal left padding is predicated loads).
 //
@@ -15,25 +16,19 @@
 //                          u0 = q + (r ? 2 : 1) and u0 - 1.  One GEMM per phase r = blockIdx.z: M = C_in, K = 2 C_out
 //                          (kk = 2 co + tap), N = B count_r, count_r the v < T of phase r; W re-packed to [r][kk][ci].  A phase's
 //                          stores are strided by s.  No structural zero is multiplied.
-//   wgrad_kernel:          dW[co][ci][j] = sum_{b,u} dy[b][co][u] a(x[b][ci][u s - (k-1-j) d]),  db[co] = sum_{b,u} dy[b][co][u]
-//                          GEMM M = C_out, N = C_in k + 1 (n = ci k + j; the last column's tap is 1: db, left out when db is
-//                          not asked for, which saves the 1x1 convs of 2^n channels a whole column tile), reduction over
-//                          rho = b T_out + u.  dy and x are contiguous along u, so the staging threads run along rho and write LDS
-//                          transposed to the MFMA's [rho][m] / [rho][n].  The reduction is cut into S slices of whole 32-deep
-//                          steps (wgrad_plan: a function of the shape only); workgroup (tile, slice) writes its f32 partial tile
-//                          to the workspace [slice][m][n].
+//   wgrad_kernel:          dW[co][ci][j] = sum_{b,u} dy[b][co][u] a(x[b][g C_in/G + ci][u s - (k-1-j) d]),  db[co] = sum_{b,u} dy[b][co][u]
+//                          for co of group g = co / (C_out/G) and ci < C_in/G.  One GEMM per group: M = C_out/G, N = (C_in/G) k + 1
+//                          (n = ci k + j; the last column's tap is 1: db, left out when db is not asked for, which saves the 1x1
+//                          convs of 2^n channels a whole column tile), reduction over rho = b T_out + u.  dy and x are contiguous
+//                          along u, so the staging threads run along rho and write LDS transposed to the MFMA's [rho][m] /
+//                          [rho][n].  The reduction is cut into S slices of whole 32-deep steps (wgrad_plan: a function of the shape
+//                          only); blockIdx.z = g S + slice; workgroup (group, tile, slice) writes its f32 partial tile to the
+//                          workspace [slice][g C_out/G + m][n]: rows of all groups side by side, the layout of dW itself.
 //   wgrad_fold_kernel:     (wgrad_fold.h, shared with dec_wgrad.hip) one thread per (m, n): the S partials in ascending slice
 //                          order in f64, rounded once, stored as dW [co][ci][k] (the reference's layout: m (C_in k) + n) or db[m].
 #include "wgrad_fold.h"
 
 namespace adk {
-
-constexpr int ENC_ACT_NONE = 0, ENC_ACT_ELU = 1;
-
-// dec_grad.hip's dec_act, restated (that file's code objects stay as they are)
-__device__ __forceinline__ float enc_act(float v, int act, float alpha) {
-    return (act == ENC_ACT_ELU && !(v > 0.f)) ? alpha * expm1_neg(v) : v;
-}
 
 struct EncDown {                                    // x [n_items][c_in][t] -> y [n_items][c_out][t_out]
     int n_items, c_in, c_out, t, t_out, ksz, stride;
@@ -127,12 +122,13 @@ __global__ __launch_bounds__(CG_THREADS) void enc_down_grad_kernel(EncDownGrad c
 struct WGrad {
     int n_items, c_in, c_out, t, t_out, ksz, dil, stride, act;
     float alpha;
-    int ck;                                         // c_in * ksz: columns 0 .. ck - 1 are dW's, column ck is db's
+    int cin_g, cout_g;                              // channels of one group
+    int ck;                                         // cin_g * ksz: columns 0 .. ck - 1 are dW's, column ck is db's
     int nc_live;                                    // columns computed: ck + 1, or ck when db is not asked for
     int red;                                        // n_items * t_out: the reduction length
     int steps_per, slices;                          // 32-deep steps of one slice, and S
     const float* dy; const float* x; float* ws;     // ws [slices][c_out][ck + 1]
-};
+};                                                  // the grid's z is groups * slices
 
 template <int WM, int WN, int TM, int TN>
 __global__ __launch_bounds__(CG_THREADS) void wgrad_kernel(WGrad c) {
@@ -149,6 +145,8 @@ __global__ __launch_bounds__(CG_THREADS) void wgrad_kernel(WGrad c) {
     const int wm = wid / WN, wn = wid % WN;
     const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
     const int kr = tid % WG_KT, row0 = tid / WG_KT;             // this thread's reduction offset in a step, and its first row
+    const int grp = blockIdx.z / c.slices, slice = blockIdx.z - grp * c.slices;
+    const int row_g = grp * c.cout_g, ch_g = grp * c.cin_g;     // the group's first dy / workspace row and first x channel
 
     // the columns this thread stages: x offset of tap (ci, j) inside an item, and the u s it needs at least
     int xoff[B_PER], need[B_PER];
@@ -158,7 +156,7 @@ __global__ __launch_bounds__(CG_THREADS) void wgrad_kernel(WGrad c) {
         const int n = n0 + row0 + i * ROWS;
         const bool tap = n < c.ck;                              // the bias column and columns past it read no x
         const int ci = n / c.ksz, back = (c.ksz - 1 - (n - ci * c.ksz)) * c.dil;
-        xoff[i] = tap ? ci * c.t - back : 0;
+        xoff[i] = tap ? (ch_g + ci) * c.t - back : 0;
         need[i] = tap ? back : 0x7fffffff;
         bias_col |= (n == c.ck && n < c.nc_live) ? 1u << i : 0u;
     }
@@ -180,8 +178,8 @@ __global__ __launch_bounds__(CG_THREADS) void wgrad_kernel(WGrad c) {
 #pragma unroll
         for (int i = 0; i < A_PER; ++i) {
             const int m = m0 + row0 + i * ROWS;
-            const bool ok = live && m < c.c_out;
-            ra[i] = dyb[ok ? (long long)m * c.t_out : 0];
+            const bool ok = live && m < c.cout_g;
+            ra[i] = dyb[ok ? (long long)(row_g + m) * c.t_out : 0];
             amask |= ok ? 1u << i : 0u;
         }
 #pragma unroll
@@ -197,7 +195,7 @@ __global__ __launch_bounds__(CG_THREADS) void wgrad_kernel(WGrad c) {
 #pragma unroll
         for (int i = 0; i < B_PER; ++i) {
             const float one = (live && (bias_col >> i & 1)) ? 1.f : 0.f;
-            Bs[kr * LDB + row0 + i * ROWS] = (bmask >> i & 1) ? enc_act(rb[i], c.act, c.alpha) : one;
+            Bs[kr * LDB + row0 + i * ROWS] = (bmask >> i & 1) ? in_act(rb[i], c.act, c.alpha) : one;
         }
     };
 
@@ -210,7 +208,7 @@ __global__ __launch_bounds__(CG_THREADS) void wgrad_kernel(WGrad c) {
             for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
 
     const int n_steps = (c.red + WG_KT - 1) / WG_KT;
-    const int s0 = blockIdx.z * c.steps_per, s1 = min(n_steps, s0 + c.steps_per);
+    const int s0 = slice * c.steps_per, s1 = min(n_steps, s0 + c.steps_per);
     const int arow = wm * TM * 32 + (lane & 31), brow = wn * TN * 32 + (lane & 31), kh = lane >> 5;
     if (s0 < s1) load(s0);
     for (int st = s0; st < s1; ++st) {
@@ -232,9 +230,9 @@ __global__ __launch_bounds__(CG_THREADS) void wgrad_kernel(WGrad c) {
         __syncthreads();
     }
 
-    // C/D map col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5); the partial tile goes to ws[slice][m][n]
+    // C/D map col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5); the partial tile goes to ws[slice][row_g + m][n]
     const int nc = c.ck + 1;
-    float* __restrict__ wsz = c.ws + (size_t)blockIdx.z * c.c_out * nc;
+    float* __restrict__ wsz = c.ws + ((size_t)slice * c.c_out + row_g) * nc;
 #pragma unroll
     for (int b = 0; b < TN; ++b) {
         const int n = n0 + wn * TN * 32 + b * 32 + (lane & 31);
@@ -244,7 +242,7 @@ __global__ __launch_bounds__(CG_THREADS) void wgrad_kernel(WGrad c) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int m = m0 + wm * TM * 32 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                if (m < c.c_out) wsz[(size_t)m * nc + n] = acc[a][b][r];
+                if (m < c.cout_g) wsz[(size_t)m * nc + n] = acc[a][b][r];
             }
     }
 }
@@ -271,26 +269,69 @@ static int enc_down_geometry(const std::string& f, int n_items, int c_in, int t,
         else hipLaunchKernelGGL((kernel<1, 4, 1, 1>), dim3(nx128, ((m) + 31) / 32, phases), dim3(CG_THREADS), 0, s, c);  \
     } while (0)
 
-// The weight gradient's checks and geometry; the slice rule is wgrad_fold.h's wgrad_slices.
-static int wgrad_plan(const std::string& f, int n_items, int c_in, int t, int c_out, int kernel, int dil, int stride, int act,
-                      float alpha, WGrad& g, long long& ws_bytes) {
+// The weight gradient's checks and geometry; the slice rule is wgrad_fold.h's wgrad_slices with the tiles of all groups.  max_act
+// is the largest act the entry point takes: IN_ACT_ELU for adk_conv_wgrad, IN_ACT_LEAKY for adk_voc_conv_wgrad.
+static int wgrad_plan(const std::string& f, int n_items, int c_in, int t, int c_out, int kernel, int dil, int stride, int groups,
+                      int act, int max_act, float alpha, WGrad& g, long long& ws_bytes) {
     if (n_items < 0 || c_in <= 0 || t <= 0 || c_out <= 0 || kernel <= 0 || dil <= 0 || stride <= 0)
         return fail(ADK_ERR_ARG, f + ": need n_items >= 0, c_in, t, c_out, kernel, dilation, stride > 0");
-    if (act != ENC_ACT_NONE && act != ENC_ACT_ELU) return fail(ADK_ERR_ARG, f + ": act must be 0 (none) or 1 (ELU)");
-    if (act == ENC_ACT_ELU && !(alpha == alpha)) return fail(ADK_ERR_ARG, f + ": alpha is NaN");
-    const int t_out = (t - 1) / stride + 1;
-    const long long red = (long long)n_items * t_out, ck = (long long)c_in * kernel;
-    if (t >= (1 << 30) || (long long)(kernel - 1) * dil >= (1LL << 30) || ck >= (1LL << 30) || (long long)c_in * t >= (1LL << 31) ||
-        red >= (1LL << 31) - WG_KT || (long long)c_out * (ck + 1) >= (1LL << 31) || (c_out + 31) / 32 > 65535)
+    if (groups < 1 || c_in % groups || c_out % groups)
+        return fail(ADK_ERR_ARG, f + ": need groups >= 1 that divides c_in and c_out");
+    if (act < IN_ACT_NONE || act > max_act)
+        return fail(ADK_ERR_ARG, f + (max_act == IN_ACT_ELU ? ": act must be 0 (none) or 1 (ELU)" : ": act must be 0 (none), 1 (ELU) or 2 (LeakyReLU)"));
+    if (act != IN_ACT_NONE && !(alpha == alpha)) return fail(ADK_ERR_ARG, f + ": alpha is NaN");
+    const int t_out = (t - 1) / stride + 1, cin_g = c_in / groups, cout_g = c_out / groups;
+    const long long red = (long long)n_items * t_out, ck = (long long)cin_g * kernel;
+    // the whole layer's c_in * kernel bounds a group's ck; c_in * t is the x offset of the last group's last channel
+    if (t >= (1 << 30) || (long long)(kernel - 1) * dil >= (1LL << 30) || (long long)c_in * kernel >= (1LL << 30) ||
+        (long long)c_in * t >= (1LL << 31) || red >= (1LL << 31) - WG_KT || (long long)c_out * (ck + 1) >= (1LL << 31) ||
+        (c_out + 31) / 32 > 65535)
         return fail(ADK_ERR_ARG, f + ": layer too large");
-    const int bm = c_out >= 128 ? 128 : c_out >= 64 ? 64 : 32;
-    const long long tiles = (long long)((c_out + bm - 1) / bm) * ((ck + 1 + 127) / 128);
+    const int bm = cout_g >= 128 ? 128 : cout_g >= 64 ? 64 : 32;
+    const long long tiles = (long long)groups * ((cout_g + bm - 1) / bm) * ((ck + 1 + 127) / 128);
     const long long n_steps = (red + WG_KT - 1) / WG_KT;
     long long steps_per = 1, slices = 1;
     wgrad_slices(tiles, n_steps, steps_per, slices);
+    if (groups * slices > 65535) return fail(ADK_ERR_ARG, f + ": layer too large (groups * slices is the grid's z)");
     g.n_items = n_items; g.c_in = c_in; g.c_out = c_out; g.t = t; g.t_out = t_out; g.ksz = kernel; g.dil = dil; g.stride = stride;
-    g.act = act; g.alpha = alpha; g.ck = (int)ck; g.nc_live = (int)ck + 1; g.red = (int)red; g.steps_per = (int)steps_per; g.slices = (int)slices;
+    g.act = act; g.alpha = alpha; g.cin_g = cin_g; g.cout_g = cout_g; g.ck = (int)ck; g.nc_live = (int)ck + 1; g.red = (int)red;
+    g.steps_per = (int)steps_per; g.slices = (int)slices;
     ws_bytes = slices * c_out * (ck + 1) * 4;
+    return ADK_OK;
+}
+
+static int conv_wgrad_plan(const std::string& f, int n_items, int c_in, int t, int c_out, int kernel, int dilation, int stride,
+                           int groups, int64_t* workspace_bytes, int32_t* slices) {
+    WGrad g;
+    long long bytes = 0;
+    const int rc = wgrad_plan(f, n_items, c_in, t, c_out, kernel, dilation, stride, groups, IN_ACT_NONE, IN_ACT_NONE, 0.f, g, bytes);
+    if (rc != ADK_OK) return rc;
+    if (workspace_bytes) *workspace_bytes = bytes;
+    if (slices) *slices = g.slices;
+    return ADK_OK;
+}
+
+static int conv_wgrad(const std::string& f, int max_act, const float* dy, const float* x, float* dw, float* db, void* workspace,
+                      int n_items, int c_in, int t, int c_out, int kernel, int dilation, int stride, int groups, int act, float alpha,
+                      void* stream) {
+    WGrad c;
+    long long bytes = 0;
+    int rc = wgrad_plan(f, n_items, c_in, t, c_out, kernel, dilation, stride, groups, act, max_act, alpha, c, bytes);
+    if (rc != ADK_OK) return rc;
+    rc = check_pointers(f, "dy/x/dw/db/workspace", !dw || !workspace || (n_items > 0 && (!dy || !x)), {dy, x, dw, db, workspace});
+    if (rc != ADK_OK) return rc;
+    c.dy = dy; c.x = x; c.ws = static_cast<float*>(workspace);
+    c.nc_live = db ? c.ck + 1 : c.ck;                          // without db its column is not computed
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DeviceGuard guard(device_of(dw));
+    const unsigned nx = (unsigned)((c.nc_live + 127) / 128), nz = (unsigned)(groups * c.slices);
+    const int m = c.cout_g;
+    if (m >= 128) hipLaunchKernelGGL((wgrad_kernel<2, 2, 2, 2>), dim3(nx, (m + 127) / 128, nz), dim3(CG_THREADS), 0, s, c);
+    else if (m >= 64) hipLaunchKernelGGL((wgrad_kernel<2, 2, 1, 2>), dim3(nx, (m + 63) / 64, nz), dim3(CG_THREADS), 0, s, c);
+    else hipLaunchKernelGGL((wgrad_kernel<1, 4, 1, 1>), dim3(nx, (m + 31) / 32, nz), dim3(CG_THREADS), 0, s, c);
+    ADK_HIP_CHECK(hipGetLastError());
+    launch_wgrad_fold(c.ws, dw, db, (int)c_out, c.ck, c.slices, s);
+    ADK_HIP_CHECK(hipGetLastError());
     return ADK_OK;
 }
 
@@ -338,36 +379,22 @@ extern "C" int adk_enc_down_grad(const float* dy, const float* w, float* dx, int
 
 extern "C" int adk_conv_wgrad_plan(int32_t n_items, int32_t c_in, int32_t t, int32_t c_out, int32_t kernel, int32_t dilation,
                                    int32_t stride, int64_t* workspace_bytes, int32_t* slices) {
-    WGrad g;
-    long long bytes = 0;
-    const int rc = wgrad_plan("adk_conv_wgrad_plan", n_items, c_in, t, c_out, kernel, dilation, stride, ENC_ACT_NONE, 0.f, g, bytes);
-    if (rc != ADK_OK) return rc;
-    if (workspace_bytes) *workspace_bytes = bytes;
-    if (slices) *slices = g.slices;
-    return ADK_OK;
+    return conv_wgrad_plan("adk_conv_wgrad_plan", n_items, c_in, t, c_out, kernel, dilation, stride, 1, workspace_bytes, slices);
 }
-
 extern "C" int adk_conv_wgrad(const float* dy, const float* x, float* dw, float* db, void* workspace, int32_t n_items, int32_t c_in,
                               int32_t t, int32_t c_out, int32_t kernel, int32_t dilation, int32_t stride, int32_t act, float alpha,
                               void* stream) {
-    const std::string f = "adk_conv_wgrad";
-    WGrad c;
-    long long bytes = 0;
-    int rc = wgrad_plan(f, n_items, c_in, t, c_out, kernel, dilation, stride, act, alpha, c, bytes);
-    if (rc != ADK_OK) return rc;
-    rc = check_pointers(f, "dy/x/dw/db/workspace", !dw || !workspace || (n_items > 0 && (!dy || !x)), {dy, x, dw, db, workspace});
-    if (rc != ADK_OK) return rc;
-    c.dy = dy; c.x = x; c.ws = static_cast<float*>(workspace);
-    c.nc_live = db ? c.ck + 1 : c.ck;                          // without db its column is not computed
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    DeviceGuard guard(device_of(dw));
-    const int nc = c.nc_live;
-    const unsigned nx = (unsigned)((nc + 127) / 128);
-    if (c_out >= 128) hipLaunchKernelGGL((wgrad_kernel<2, 2, 2, 2>), dim3(nx, (c_out + 127) / 128, c.slices), dim3(CG_THREADS), 0, s, c);
-    else if (c_out >= 64) hipLaunchKernelGGL((wgrad_kernel<2, 2, 1, 2>), dim3(nx, (c_out + 63) / 64, c.slices), dim3(CG_THREADS), 0, s, c);
-    else hipLaunchKernelGGL((wgrad_kernel<1, 4, 1, 1>), dim3(nx, (c_out + 31) / 32, c.slices), dim3(CG_THREADS), 0, s, c);
-    ADK_HIP_CHECK(hipGetLastError());
-    launch_wgrad_fold(c.ws, dw, db, (int)c_out, c.ck, c.slices, s);
-    ADK_HIP_CHECK(hipGetLastError());
-    return ADK_OK;
+    return conv_wgrad("adk_conv_wgrad", IN_ACT_ELU, dy, x, dw, db, workspace, n_items, c_in, t, c_out, kernel, dilation, stride, 1, act,
+                      alpha, stream);
+}
+
+extern "C" int adk_voc_conv_wgrad_plan(int32_t n_items, int32_t c_in, int32_t t, int32_t c_out, int32_t kernel, int32_t dilation,
+                                       int32_t groups, int64_t* workspace_bytes, int32_t* slices) {
+    return conv_wgrad_plan("adk_voc_conv_wgrad_plan", n_items, c_in, t, c_out, kernel, dilation, 1, groups, workspace_bytes, slices);
+}
+extern "C" int adk_voc_conv_wgrad(const float* dy, const float* x, float* dw, float* db, void* workspace, int32_t n_items,
+                                  int32_t c_in, int32_t t, int32_t c_out, int32_t kernel, int32_t dilation, int32_t groups,
+                                  int32_t act, float alpha, void* stream) {
+    return conv_wgrad("adk_voc_conv_wgrad", IN_ACT_LEAKY, dy, x, dw, db, workspace, n_items, c_in, t, c_out, kernel, dilation, 1, groups,
+                      act, alpha, stream);
 }

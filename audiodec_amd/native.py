@@ -116,7 +116,14 @@ SYMBOLS = {
     "adk_conv_wgrad": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float, _vp]),
     "adk_convtr_wgrad_plan": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i64), C.POINTER(_i32)]),
     "adk_convtr_wgrad": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float, _vp]),
-    "adk_packed_weight_floats_split16": (C.c_int64, [_i32, _i32, _i32]),
+    "adk_voc_conv": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float, _i32, _vp]),
+    "adk_voc_conv_grad": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float, _vp]),
+    "adk_voc_convtr": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float, _vp]),
+    "adk_voc_convtr_grad": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float, _vp]),
+    "adk_voc_conv_wgrad_plan": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i64), C.POINTER(_i32)]),
+    "adk_voc_conv_wgrad": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float, _vp]),
+    "adk_voc_convtr_wgrad": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float, _vp]),
+    "adk_packed_weight_floats_split16":(C.c_int64, [_i32, _i32, _i32]),
     "adk_pack_weights_split16": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "adk_codes_frame_bytes": (C.c_int32, [_i32, _i32]),
     "adk_codes_pack": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),

@@ -539,6 +539,47 @@ int adk_convtr_wgrad(const float* dy, const float* x, float* dw, float* db, void
                      int32_t c_out, int32_t kernel, int32_t stride, int32_t act, float alpha, void* stream);
 
 /*
+ * The HiFi-GAN vocoder's training layers (models/vocoder/HiFiGAN.py:28-161, modules/multi_fusion.py, modules/residual_block.py):
+ * the seven calls above with two extensions, on the same kernels (the adk_dec_* / adk_conv_wgrad / adk_convtr_wgrad calls are
+ * these with groups = 1 and act <= 1, and their results are what they were).  Exact f32, no atomics, every output element written
+ * once, every split of a sum a function of the shape alone: bitwise reproducible.
+ * act: 0 = none, 1 = ELU(alpha) as above, 2 = LeakyReLU with slope alpha: a(x) = x > 0 ? x : alpha x, a'(x) = x > 0 ? 1 : alpha
+ *   (the derivative at 0 is the slope, as torch's is).  x is read, and required, by the two _grad calls whenever act != 0.
+ * groups = G >= 1 dividing c_in and c_out (the stride-1 calls): group g maps input channels [g c_in/G, (g+1) c_in/G) to output
+ *   channels [g c_out/G, (g+1) c_out/G); with g = o / (c_out/G) and ci over c_in/G:
+ *   adk_voc_conv:        y[b][o][u] = bias[o] + sum_{ci, j} W[o][ci][j] a(x[b][g c_in/G + ci][u - (kernel-1-j) dilation]) + res[b][o][u]
+ *                        impl 2 (gemm): w is [G][(ci, j) at ci kernel + j][c_out/G].  impl 1 (direct): G == 1 only, meant for c_out <= 2.
+ *   adk_voc_conv_grad:   dx[b][g c_in/G + ci][u] = a'(x[..]) sum_{o in g, j} W[o][ci][j] dy[b][o][u + (kernel-1-j) dilation] + dres[..]
+ *                        w is [G][(o, j) at (o - g c_out/G) kernel + j][c_in/G].
+ *   adk_voc_conv_wgrad:  dw[o][ci][j] = sum_{b,u} dy[b][o][u] a(x[b][g c_in/G + ci][u - (kernel-1-j) dilation]), db[o] = sum_{b,u} dy[b][o][u]
+ *                        dw [c_out][c_in/G][kernel], the reference's layout; stride 1.  workspace: adk_voc_conv_wgrad_plan's bytes,
+ *                        laid out [slice][c_out][c_in/G kernel + 1], so one fold serves all groups.
+ *   adk_voc_conv_wgrad_plan: host only.  adk_conv_wgrad_plan's rule with tiles = G ceil((c_out/G) / BM) ceil((c_in/G kernel + 1) / 128),
+ *                        BM = 128 / 64 / 32 from c_out/G >= 128 / >= 64 / below; *workspace_bytes = 4 S c_out (c_in/G kernel + 1).
+ * adk_voc_convtr, adk_voc_convtr_grad, adk_voc_convtr_wgrad: adk_dec_convtr, adk_dec_convtr_grad and adk_convtr_wgrad (one group,
+ *   kernel == 2 stride, the same packings; the plan is adk_convtr_wgrad_plan's) with act 0, 1 or 2.
+ * n_items == 0 is a no-op of the forward and _grad calls and writes zeros for the weight gradients.  Every argument is checked
+ * before any HIP call (ADK_ERR_ARG).  No allocation, no synchronisation.
+ */
+int adk_voc_conv(const float* x, const float* w, const float* bias, const float* res, float* y, int32_t n_items, int32_t c_in,
+                 int32_t t, int32_t c_out, int32_t kernel, int32_t dilation, int32_t groups, int32_t act, float alpha, int32_t impl,
+                 void* stream);
+int adk_voc_conv_grad(const float* dy, const float* x, const float* w, const float* dres, float* dx, int32_t n_items,
+                      int32_t c_in, int32_t t, int32_t c_out, int32_t kernel, int32_t dilation, int32_t groups, int32_t act,
+                      float alpha, void* stream);
+int adk_voc_convtr(const float* x, const float* w, const float* bias, float* y, int32_t n_items, int32_t c_in, int32_t t,
+                   int32_t c_out, int32_t kernel, int32_t stride, int32_t act, float alpha, void* stream);
+int adk_voc_convtr_grad(const float* dy, const float* x, const float* w, float* dx, int32_t n_items, int32_t c_in, int32_t t,
+                        int32_t c_out, int32_t kernel, int32_t stride, int32_t act, float alpha, void* stream);
+int adk_voc_conv_wgrad_plan(int32_t n_items, int32_t c_in, int32_t t, int32_t c_out, int32_t kernel, int32_t dilation,
+                            int32_t groups, int64_t* workspace_bytes, int32_t* slices);
+int adk_voc_conv_wgrad(const float* dy, const float* x, float* dw, float* db, void* workspace, int32_t n_items, int32_t c_in,
+                       int32_t t, int32_t c_out, int32_t kernel, int32_t dilation, int32_t groups, int32_t act, float alpha,
+                       void* stream);
+int adk_voc_convtr_wgrad(const float* dy, const float* x, float* dw, float* db, void* workspace, int32_t n_items, int32_t c_in,
+                         int32_t t, int32_t c_out, int32_t kernel, int32_t stride, int32_t act, float alpha, void* stream);
+
+/*
  * Multi-resolution STFT loss and waveform-shape loss, one resolution / one window length per call (losses/stft_loss.py:19-170,
  * losses/waveform_loss.py:15-75).  The STFT is adk_logmel's: torch.stft's defaults, the window [win_length] centred in n_fft,
  * 1 + n_samples/hop frames, n_fft/2 + 1 bins, mag = sqrt(max(re^2 + im^2, eps)) (a NaN stays NaN).
