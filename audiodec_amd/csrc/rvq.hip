@@ -125,6 +125,9 @@ __global__ __launch_bounds__(RVQ_THREADS) void rvq_encode_kernel(const float* __
         if (tid < RB) {
             float v = red_v[tid][0]; int i = red_i[tid][0];
             for (int w = 1; w < RVQ_WAVES; ++w) argmax_merge(v, i, red_v[tid][w], red_i[tid][w]);
+            // no distance of the row compared (every one NaN: a NaN component, or |r|^2 and 2rE both overflowed) leaves the start value
+            // 0x7fffffff: such a row takes code 0 of the stage, as (-dist).max(1) and the v3/v4 kernels below do, and the gather stays inside E
+            i = (unsigned)i < (unsigned)size ? i : 0;
             best_sh[tid] = i;
             if (row0 + tid < n_rows) idx[(size_t)st * n_rows + row0 + tid] = (long long)i + (long long)size * st;
         }
