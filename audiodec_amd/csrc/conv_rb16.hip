@@ -27,7 +27,8 @@
 // Columns of the implicit GEMM are (stream, step) pairs packed densely (n = s * T + t), so several streams of a short
 // frame share a 32-column MFMA tile (128-channel layers: 2 streams x 25 steps per workgroup).
 // Per output element the operations and their order are exactly those of conv_rl16 (k ascending, acc0 + acc1/2048, + bias,
-// + residual): the result is BIT-IDENTICAL to the per-op path (tests/test_gpu_b256.py::test_residual_chains_are_bit_identical).
+// + residual): the result is BIT-IDENTICAL to the per-op path (tests/test_gpu_b256.py::test_residual_chains_are_bit_identical; every template
+// arm of launch_conv_rb16, against an exact model as well: tests/test_gpu_chain_variants.py).
 #include "conv_split16.h"      // the operand format, act_split / join4 / not_finite4, ADK_LDS_DMA16, wait_vm
 
 #ifndef ADK_RB16_PF32
@@ -82,6 +83,9 @@ namespace {
 constexpr int kRbMaxConvs = 8;
 constexpr int kRbMaxHist = 56;           // rows of causal history a conv of the chain may need ((K-1) * dilation: 54 for K7 d9, 50 for K11 d5)
 constexpr int kRbTouchSink = 256;      // bytes at the end of the dynamic LDS that the L2 warm-up touches (LDS-DMA loads nobody reads) land in
+// 8-channel history pieces PER THREAD an instantiation stages in registers (hist_issue / hist_commit): room for smax streams of the longest history.
+// rb_plan checks every launch against it -- a plan that needs more pieces than its instantiation holds is refused, never truncated.
+constexpr int rb_hist_pieces(int C, int smax) { return (smax * kRbMaxHist * (C / 8) + 255) / 256; }
 
 struct RbNode {                          // a tensor of the chain: where its rows live in HBM (a state ring)
     float* base; int rows, ch, cursor, choff, gstride;      // row of step t of stream b: base + (b * rows + (cursor + t) mod rows) * ch + choff + g * gstride
@@ -253,7 +257,8 @@ __global__ __launch_bounds__(256, WPS) void conv_rb16_kernel(RbArgs r) {
     constexpr bool BIAS_LATE = WR > 0 && !BIAS_LDS;
     constexpr bool HIST_LATE = (((WR > 0 || ADK_RB16_HIST_LATE > 1) && WPS == 3) || (C == 128 && ADK_RB16_HIST_LATE128)) && ADK_RB16_HIST_LATE;   // 168-register ring variants: the next conv's history rows are requested BEHIND the
                                                      // finish / ring-store pass instead of in front of it (16 registers less at the epilogue's peak)   // bias fetched BEHIND the MFMA loop (16 registers per lane would otherwise live through it)
-    constexpr int NHP = (SMAX * kRbMaxHist * C8 + NT - 1) / NT;      // 8-channel history pieces per thread
+    constexpr int NHP = rb_hist_pieces(C, SMAX);                    // 8-channel history pieces per thread
+    static_assert(NT == 256, "rb_hist_pieces counts pieces per thread of a 256-thread workgroup");
     extern __shared__ __attribute__((aligned(16))) unsigned char xs[];
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -673,7 +678,30 @@ __global__ __launch_bounds__(256, WPS) void conv_rb16_kernel(RbArgs r) {
     if (bad) atomicOr(r.err, 8);
 }
 
-struct RbPlan { int C, ta, tb, ntw, spw, n_tiles, hm, rps, wr; size_t lds; long long blocks; };
+// The template arm a launch runs on (adk_conv_rb16_plan reports it; values are part of that function's contract).
+enum RbArm : int {
+    kRbArmNone = 0,
+    kRb32Ring = 1,          // 32 channels, two tiles per wave, shared LDS weight ring, 168 registers
+    kRb32Few2 = 2,          // 32 channels, two tiles, <= 128 workgroups: weights into registers, 256 registers
+    kRb32Three11 = 3,       // 32 channels, three tiles, K11: residual fetched behind the second conv's loop
+    kRb32Three = 4,         // 32 channels, three tiles, the other tap sets: residual fetched under the loop
+    kRb32Four = 5,          // 32 channels, four tiles
+    kRb64Ring = 6,          // 64 channels, two tiles, weight ring, 168 registers
+    kRb64Few2 = 7,          // 64 channels, two tiles, <= 128 workgroups, 256 registers
+    kRb64Three = 8,         // 64 channels, three tiles
+    kRb64Four = 9,          // 64 channels, four tiles
+    kRb128One = 10,         // 128 channels, one stream per workgroup, one tile per wave
+    kRb128Two = 11,         // 128 channels, two tiles per wave (one long stream or two streams)
+    kRb128One2 = 12,        // 128 channels, two streams of <= 16 steps in one tile per wave
+    kRbArmCount = 13
+};
+
+// streams per workgroup an arm's register staging of history rows is sized for (SMAX of its instantiation)
+constexpr int rb_arm_smax(int arm) {
+    return (arm == kRb64Three || arm == kRb64Four || arm == kRb128Two || arm == kRb128One2) ? 2 : 1;
+}
+
+struct RbPlan { int C, ta, tb, ntw, spw, n_tiles, hm, rps, wr, arm; size_t lds; long long blocks; };
 
 int rb_streams_per_wg(int C, int batch, int t, int groups) {
     int s = (C == 128) ? 2 : 1;
@@ -706,10 +734,54 @@ int rb_ring_slots(int C, int ntw, int spw, long long blocks) {
     return 0;
 }
 
-// Geometry of the launch, or false when the chain does not fit this kernel for this call.
+// The arm for a geometry rb_plan has filled in (C, ta, ntw, spw, wr, blocks): the ONE place that decides which instantiation runs --
+// launch_conv_rb16 switches on its result, adk_conv_rb16_plan reports it.
+// Register budgets.  Two n-tiles per wave: 168 registers (three 4-wave workgroups per CU), the residual fetched under the second
+// conv's MFMAs; three: 256 (two workgroups), residual early; four: 256, residual after the loop.  128 channels: 256, prefetch
+// distance 3 steps (ADK_RB16_PF128), and the waves re-align every 4 steps (LS).
+// (32 channels used to run as 5 waves x 2 tiles: the hardware starts every workgroup's waves on the same SIMD, so one SIMD
+// carried two waves of every co-resident workgroup and a second 5-wave workgroup did not even fit at 168 registers --
+// profiles/r3_rb16_timeline.md.  Now 4 waves x (3, 3, 2, 2) tiles, the odd tiles rotating with the workgroup.)
+// Round 4: with the shared LDS weight ring (pl.wr slots, rb_mfma_ring) no weight fragment lives in registers -- the PF argument is
+// then unused (1) -- and the 168-register variants have room for the residual again.
+// Launches of <= 128 workgroups, round 5: no ring -- and no reason to squeeze the two-tile variants into 168 registers for a third workgroup per CU
+// that never comes: the 256-register builds of the same code have no spills, the 168-register ones 30-33 spilled registers without the ring.
+// Two tiles per wave at 32 / 64 channels is therefore either the ring arm (> 128 workgroups: rb_ring_slots) or the `few` arm -- the 168-register
+// builds without a ring that used to sit between them could not be reached and are gone (tests/test_chain_cases.py sweeps the plan).
+int rb_choose_arm(const RbPlan& pl) {
+    const bool few = pl.blocks <= 128;
+    if (pl.C == 32) {
+        if (pl.wr > 0) return kRb32Ring;                    // (rb_ring_slots: two tiles per wave only)
+        if (pl.ntw == 2) return few ? kRb32Few2 : kRbArmNone;
+        // (three tiles, K11 blocks of the vocoder: with the residual fetched AFTER the second conv's loop the kernel has 1 spilled register
+        // instead of 45 -- stage-3 chain 151.6 -> 142.5 us, pipeline +1.2 % on one box; the K7 + 1x1 units of the encoder have no spills
+        // either way and lose 2 us with the late fetch)
+        if (pl.ntw == 3) return pl.ta == 11 ? kRb32Three11 : kRb32Three;
+        return pl.ntw == 4 ? kRb32Four : kRbArmNone;
+    }
+    if (pl.C == 64) {
+        if (pl.wr > 0) return kRb64Ring;
+        if (pl.ntw == 2 && pl.spw == 1) return few ? kRb64Few2 : kRbArmNone;
+        if (pl.ntw <= 3) return kRb64Three;
+        return pl.ntw == 4 ? kRb64Four : kRbArmNone;
+    }
+    if (pl.C != 128) return kRbArmNone;
+    // few streams: one stream, one tile per wave.  (Deeper weight prefetch for these one-workgroup-per-CU launches -- 8 steps at 128 channels, 4 at 32, five
+    // ring slots at 64 -- measured 1-2 % SLOWER at 1 / 8 / 32 / 64 streams, round 5: the stream of one workgroup per CU is not bound by its round trips.)
+    // Two streams of at most 16 steps share the one tile of a full launch: their history rows need the staging of two streams (kRb128One2).
+    if (pl.ntw == 1) return pl.spw == 1 ? kRb128One : kRb128One2;
+    return pl.ntw == 2 ? kRb128Two : kRbArmNone;
+}
+
+// 8-channel history pieces the workgroup's threads hold between them in the arm's instantiation / that the launch needs for its longest history
+long long rb_arm_hist_capacity(int C, int arm) { return 256ll * rb_hist_pieces(C, rb_arm_smax(arm)); }
+long long rb_hist_needed(const RbPlan& pl) { return (long long)pl.spw * pl.hm * (pl.C / 8); }
+
+// Geometry of the launch, or false when the chain does not fit this kernel for this call.  Shape only: channels, taps, dilations, batch, groups, steps.
 bool rb_plan(const ConvArgs* c, int n, RbPlan& pl) {
     const ConvArgs& a0 = c[0];
     pl.C = a0.cin_g; pl.ta = a0.taps; pl.tb = c[1].taps;
+    pl.arm = kRbArmNone;
     const int T = a0.t_out;
     const int wm = 4 / (pl.C / 32);
     pl.spw = rb_streams_per_wg(pl.C, a0.batch, T, a0.groups);
@@ -720,12 +792,67 @@ bool rb_plan(const ConvArgs* c, int n, RbPlan& pl) {
     for (int k = 0; k < n; ++k) pl.hm = std::max(pl.hm, (c[k].taps - 1) * c[k].dilation);
     if (pl.hm > kRbMaxHist) return false;
     pl.rps = pl.hm + T;
-    pl.wr = rb_ring_slots(pl.C, pl.ntw, pl.spw, (long long)((a0.batch + pl.spw - 1) / pl.spw) * a0.groups);
-    const bool bias_lds = pl.C < 128 && !(pl.C == 64 && (pl.spw > 1 || pl.ntw > 2 || pl.wr > 0));        // (as BIAS_LDS of the instantiation rb_by_taps picks)
-    pl.lds = (size_t)pl.spw * pl.rps * (4 * pl.C + 16) + (bias_lds ? (size_t)n * pl.C * 4 : 0) + (size_t)pl.wr * 4096 + kRbTouchSink;
-    if (pl.lds > 160 * 1024 || pl.spw > (pl.C == 128 ? 2 : (pl.C == 64 ? 2 : 1))) return false;      // (SMAX of the instantiations)
     pl.blocks = (long long)((a0.batch + pl.spw - 1) / pl.spw) * a0.groups;
-    return pl.blocks <= 0x7fffffffLL;
+    pl.wr = rb_ring_slots(pl.C, pl.ntw, pl.spw, pl.blocks);
+    const bool bias_lds = pl.C < 128 && !(pl.C == 64 && (pl.spw > 1 || pl.ntw > 2 || pl.wr > 0));        // (as BIAS_LDS of the instantiation rb_choose_arm picks)
+    pl.lds = (size_t)pl.spw * pl.rps * (4 * pl.C + 16) + (bias_lds ? (size_t)n * pl.C * 4 : 0) + (size_t)pl.wr * 4096 + kRbTouchSink;
+    if (pl.lds > 160 * 1024) return false;
+    if (pl.blocks > 0x7fffffffLL) return false;
+    pl.arm = rb_choose_arm(pl);
+    if (pl.arm == kRbArmNone) return false;
+    // the instantiation must hold the history rows of every stream of a workgroup: hist_issue / hist_commit stop at its piece count
+    if (pl.spw > rb_arm_smax(pl.arm) || rb_hist_needed(pl) > rb_arm_hist_capacity(pl.C, pl.arm)) return false;
+    return true;
+}
+
+// channels / activation / tap sets the kernel is instantiated for
+bool rb_shape_ok(int C, int act, int ta, int tb, int n) {
+    if (n < 2 || n > kRbMaxConvs || (n & 1)) return false;
+    if (C != 32 && C != 64 && C != 128) return false;
+    if (act != ADK_ACT_ELU && act != ADK_ACT_LEAKY) return false;
+    if (!((ta == 11 && tb == 11) || (ta == 7 && tb == 7) || (ta == 3 && tb == 3) || (ta == 7 && tb == 1))) return false;
+    if (act == ADK_ACT_ELU && !(ta == 7 && tb == 1)) return false;          // instantiated: ELU residual units, LeakyReLU residual blocks
+    if (act == ADK_ACT_LEAKY && tb == 1) return false;
+    return true;
+}
+
+// What the launch does beside computing: L2 warm-up touches and helper workgroups (see the kernel head).  ksteps[k]: 16-k steps of conv k.
+struct RbSchedule { int warm, n_main, helpers, helper_convs; unsigned grid; };
+RbSchedule rb_schedule(const RbPlan& pl, int groups, int n, const int* ksteps) {
+    RbSchedule sc;
+    // L2 warm-up where a conv's weight block is a few loads per lane (32 / 64 channels) AND the launch is one workgroup per CU or
+    // less (the encoder's chains: 256 workgroups, every round trip exposed -- encoder block 1 64 -> 68 us without it).  A touch is one
+    // dword per 128-byte line, i.e. 64 cache lines per wave instruction: with three workgroups per CU starting at once the ~27 touch
+    // instructions per wave in front of the staging loads cost more than they save -- round 4, after the pinned prefetch and the
+    // weight ring: vocoder stage 2 (768 workgroups) stage-in 16.7 us, chain 168 -> 152 us without the touches, stage 3 139 -> 137.
+    // The 128-channel chains would spend 22 line touches per lane and conv on it (17 us of prologue, no gain in the loops:
+    // profiles/r3_rb16_timeline.md) -- their waves walk the weights in lockstep instead (LS).
+    // Round 5: not for launches of <= 128 workgroups either (few streams) -- there the touches cost more than they save: 1 / 8 / 32 streams
+    // 0.719 / 0.750 / 0.772 ms per step with them, 0.713 / 0.746 / 0.761 without (experiments/sessions/r5_s11.sh); with them on the 128-channel chains too: 0.760 / 0.824 / 0.818.
+    sc.warm = pl.C <= 64 && pl.blocks <= 384 && pl.blocks > 128;
+    // helper workgroups (see the kernel head): launches of at most kHelperBlocks computing workgroups; per XCD the weights of the groups it hosts
+    // must fit its L2 beside everything else: the longest prefix of convs within kHelperBytes.
+    constexpr int kHelpersPerXcd = 4, kHelperBlocks = 64;
+    constexpr long long kHelperBytes = 3584 * 1024;
+    sc.n_main = (int)pl.blocks; sc.helpers = 0; sc.helper_convs = 0;
+    if (pl.blocks <= kHelperBlocks && groups <= 32) {
+        int worst = 0;                                   // most distinct groups on one XCD
+        for (int x = 0; x < 8; ++x) {
+            unsigned seen = 0; int cnt = 0;
+            for (long long i = x; i < pl.blocks; i += 8) { const unsigned bit = 1u << (int)(i % groups); if (!(seen & bit)) { seen |= bit; ++cnt; } }
+            worst = std::max(worst, cnt);
+        }
+        long long bytes = 0;
+        int kc = 0;
+        for (; kc < n; ++kc) {
+            const long long one = (long long)(pl.C / 32) * ksteps[kc] * 2048ll * worst;
+            if (bytes + one > kHelperBytes) break;
+            bytes += one;
+        }
+        if (kc > 0 && worst > 0) { sc.helpers = kHelpersPerXcd; sc.helper_convs = kc; }
+    }
+    sc.grid = sc.helpers > 0 ? (unsigned)(((sc.n_main + 7) & ~7) + 8 * sc.helpers) : (unsigned)pl.blocks;
+    return sc;
 }
 
 }  // namespace
@@ -735,12 +862,8 @@ bool conv_rb16_fusable(const ConvArgs* c, int n) {
     if (n < 2 || n > kRbMaxConvs || (n & 1)) return false;
     const ConvArgs& a0 = c[0];
     const int C = a0.cin_g;
-    if (C != 32 && C != 64 && C != 128) return false;
-    if (a0.act_in != ADK_ACT_ELU && a0.act_in != ADK_ACT_LEAKY) return false;
     const int ta = a0.taps, tb = c[1].taps;
-    if (!((ta == 11 && tb == 11) || (ta == 7 && tb == 7) || (ta == 3 && tb == 3) || (ta == 7 && tb == 1))) return false;
-    if (a0.act_in == ADK_ACT_ELU && !(ta == 7 && tb == 1)) return false;          // instantiated: ELU residual units, LeakyReLU residual blocks
-    if (a0.act_in == ADK_ACT_LEAKY && tb == 1) return false;
+    if (!rb_shape_ok(C, a0.act_in, ta, tb, n)) return false;
     if (a0.t_out < 1 || a0.batch < 1) return false;
     for (int k = 0; k < n; ++k) {
         const ConvArgs& a = c[k];
@@ -771,7 +894,7 @@ bool conv_rb16_fusable(const ConvArgs* c, int n) {
 
 namespace {
 template <int C, int ACT, int TA, int TB, int NTW, int SMAX, int WPS, int PF, bool EARLY_RES, int LS, int WR>
-int rb_go(const RbArgs& r, const RbPlan& pl, hipStream_t s) {
+int rb_go(const RbArgs& r, const RbPlan& pl, unsigned grid, hipStream_t s) {
     auto kern = conv_rb16_kernel<C, ACT, TA, TB, NTW, SMAX, WPS, PF, EARLY_RES, LS, WR>;
     if (pl.lds > 64 * 1024) {
         static bool attr_set_dev[kMaxDevices] = {};     // function attributes are per device
@@ -781,18 +904,19 @@ int rb_go(const RbArgs& r, const RbPlan& pl, hipStream_t s) {
             attr_set = true;
         }
     }
-    const unsigned grid = r.helpers > 0 ? (unsigned)(((r.n_main + 7) & ~7) + 8 * r.helpers) : (unsigned)pl.blocks;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), pl.lds, s, r);
     ADK_HIP_CHECK(hipGetLastError());
     return ADK_OK;
 }
 
-template <int C, int NTW, int SMAX, int WPS, int PF, bool EARLY_RES, int LS, int WR = 0>
-int rb_by_taps(const RbArgs& r, const RbPlan& pl, int act, hipStream_t s) {
-    if (act == ADK_ACT_ELU) return rb_go<C, ADK_ACT_ELU, 7, 1, NTW, SMAX, WPS, PF, EARLY_RES, LS, WR>(r, pl, s);
-    if (pl.ta == 11) return rb_go<C, ADK_ACT_LEAKY, 11, 11, NTW, SMAX, WPS, PF, EARLY_RES, LS, WR>(r, pl, s);
-    if (pl.ta == 7) return rb_go<C, ADK_ACT_LEAKY, 7, 7, NTW, SMAX, WPS, PF, EARLY_RES, LS, WR>(r, pl, s);
-    return rb_go<C, ADK_ACT_LEAKY, 3, 3, NTW, SMAX, WPS, PF, EARLY_RES, LS, WR>(r, pl, s);
+// ARM fixes SMAX (rb_arm_smax: what rb_plan checked the launch against); the other arguments are the arm's tuning
+template <int C, int ARM, int NTW, int WPS, int PF, bool EARLY_RES, int LS, int WR = 0>
+int rb_by_taps(const RbArgs& r, const RbPlan& pl, unsigned grid, int act, hipStream_t s) {
+    constexpr int SMAX = rb_arm_smax(ARM);
+    if (act == ADK_ACT_ELU) return rb_go<C, ADK_ACT_ELU, 7, 1, NTW, SMAX, WPS, PF, EARLY_RES, LS, WR>(r, pl, grid, s);
+    if (pl.ta == 11) return rb_go<C, ADK_ACT_LEAKY, 11, 11, NTW, SMAX, WPS, PF, EARLY_RES, LS, WR>(r, pl, grid, s);
+    if (pl.ta == 7) return rb_go<C, ADK_ACT_LEAKY, 7, 7, NTW, SMAX, WPS, PF, EARLY_RES, LS, WR>(r, pl, grid, s);
+    return rb_go<C, ADK_ACT_LEAKY, 3, 3, NTW, SMAX, WPS, PF, EARLY_RES, LS, WR>(r, pl, grid, s);
 }
 }  // namespace
 
@@ -808,6 +932,7 @@ int launch_conv_rb16(const ConvArgs* c, int n, const int* keep, hipStream_t s) {
     r.node[0].base = const_cast<float*>(a0.in); r.node[0].rows = a0.in_rows; r.node[0].ch = a0.in_ch;
     r.node[0].cursor = (a0.in_row0 + (a0.taps - 1) * a0.dilation) % a0.in_rows;
     r.node[0].choff = a0.in_choff; r.node[0].gstride = a0.in_gstride; r.node[0].keep = 0;
+    int ksteps[kRbMaxConvs];
     for (int k = 0; k < n; ++k) {
         const ConvArgs& a = c[k];
         RbNode& nd = r.node[k + 1];
@@ -817,80 +942,34 @@ int launch_conv_rb16(const ConvArgs* c, int n, const int* keep, hipStream_t s) {
         cv.wfrag = a.wfrag; cv.bias = a.bias; cv.dil = a.dilation; cv.hist = (a.taps - 1) * a.dilation;
         cv.ksteps = (a.ktot + 63) / 64 * 4;
         cv.w_bytes = (unsigned)((unsigned long long)a.groups * (a.cout_g / 32) * cv.ksteps * 2048ull);
+        ksteps[k] = cv.ksteps;
     }
     r.n_convs = n; r.batch = a0.batch; r.t = a0.t_out; r.groups = a0.groups;
     r.spw = pl.spw; r.hm = pl.hm; r.rps = pl.rps; r.n_tiles = pl.n_tiles;
     r.slope = a0.slope; r.err = conv_err_word(a0);
-    // L2 warm-up where a conv's weight block is a few loads per lane (32 / 64 channels) AND the launch is one workgroup per CU or
-    // less (the encoder's chains: 256 workgroups, every round trip exposed -- encoder block 1 64 -> 68 us without it).  A touch is one
-    // dword per 128-byte line, i.e. 64 cache lines per wave instruction: with three workgroups per CU starting at once the ~27 touch
-    // instructions per wave in front of the staging loads cost more than they save -- round 4, after the pinned prefetch and the
-    // weight ring: vocoder stage 2 (768 workgroups) stage-in 16.7 us, chain 168 -> 152 us without the touches, stage 3 139 -> 137.
-    // The 128-channel chains would spend 22 line touches per lane and conv on it (17 us of prologue, no gain in the loops:
-    // profiles/r3_rb16_timeline.md) -- their waves walk the weights in lockstep instead (LS).
-    // Round 5: not for launches of <= 128 workgroups either (few streams) -- there the touches cost more than they save: 1 / 8 / 32 streams
-    // 0.719 / 0.750 / 0.772 ms per step with them, 0.713 / 0.746 / 0.761 without (experiments/sessions/r5_s11.sh); with them on the 128-channel chains too: 0.760 / 0.824 / 0.818.
-    r.warm = pl.C <= 64 && pl.blocks <= 384 && pl.blocks > 128;
+    const RbSchedule sc = rb_schedule(pl, a0.groups, n, ksteps);
+    r.warm = sc.warm; r.n_main = sc.n_main; r.helpers = sc.helpers; r.helper_convs = sc.helper_convs;
 #if ADK_RB16_DBG & 1
     r.dbg_slot = g_rb_launch++;
 #endif
-    {
-        // helper workgroups (see the kernel head): launches of at most kHelperBlocks computing workgroups; per XCD the weights of the groups it hosts
-        // must fit its L2 beside everything else: the longest prefix of convs within kHelperBytes.
-        constexpr int kHelpersPerXcd = 4, kHelperBlocks = 64;
-        constexpr long long kHelperBytes = 3584 * 1024;
-        r.n_main = (int)pl.blocks; r.helpers = 0; r.helper_convs = 0;
-        if (pl.blocks <= kHelperBlocks && a0.groups <= 32) {
-            int worst = 0;                                   // most distinct groups on one XCD
-            for (int x = 0; x < 8; ++x) {
-                unsigned seen = 0; int cnt = 0;
-                for (long long i = x; i < pl.blocks; i += 8) { const unsigned bit = 1u << (int)(i % a0.groups); if (!(seen & bit)) { seen |= bit; ++cnt; } }
-                worst = std::max(worst, cnt);
-            }
-            long long bytes = 0;
-            int kc = 0;
-            for (; kc < n; ++kc) {
-                const long long one = (long long)(pl.C / 32) * r.conv[kc].ksteps * 2048ll * worst;
-                if (bytes + one > kHelperBytes) break;
-                bytes += one;
-            }
-            if (kc > 0 && worst > 0) { r.helpers = kHelpersPerXcd; r.helper_convs = kc; }
-        }
-    }
     const int act = a0.act_in;
-    // Register budgets.  Two n-tiles per wave: 168 registers (three 4-wave workgroups per CU), the residual fetched under the second
-    // conv's MFMAs; three: 256 (two workgroups), residual early; four: 256, residual after the loop.  128 channels: 256, prefetch
-    // distance 3 steps (ADK_RB16_PF128), and the waves re-align every 4 steps (LS).
-    // (32 channels used to run as 5 waves x 2 tiles: the hardware starts every workgroup's waves on the same SIMD, so one SIMD
-    // carried two waves of every co-resident workgroup and a second 5-wave workgroup did not even fit at 168 registers --
-    // profiles/r3_rb16_timeline.md.  Now 4 waves x (3, 3, 2, 2) tiles, the odd tiles rotating with the workgroup.)
-    // Round 4: with the shared LDS weight ring (pl.wr slots, rb_mfma_ring) no weight fragment lives in registers -- the PF argument is
-    // then unused (1) -- and the 168-register variants have room for the residual again.
-    if (pl.C == 32 && pl.wr > 0) return rb_by_taps<32, 2, 1, 3, 1, true, 0, 3>(r, pl, act, s);        // (rb_ring_slots: two tiles per wave only)
-    if (pl.C == 64 && pl.wr > 0) return rb_by_taps<64, 2, 1, 3, 1, ADK_RB16_EARLY64, 0, 3>(r, pl, act, s);
-    // (launches of <= 128 workgroups, round 5: no ring -- and no reason to squeeze the two-tile variants into 168 registers for a third workgroup per CU
-    // that never comes: the 256-register builds of the same code have no spills, the 168-register ones 30-33 spilled registers without the ring)
-    const bool few = pl.blocks <= 128;
-    if (pl.C == 32) {
-        if (pl.ntw == 2 && few) return rb_by_taps<32, 2, 1, 2, ADK_RB16_PF32, true, 0>(r, pl, act, s);
-        if (pl.ntw == 2) return rb_by_taps<32, 2, 1, 3, ADK_RB16_PF32, true, 0>(r, pl, act, s);
-        // (three tiles, K11 blocks of the vocoder: with the residual fetched AFTER the second conv's loop the kernel has 1 spilled register
-        // instead of 45 -- stage-3 chain 151.6 -> 142.5 us, pipeline +1.2 % on one box; the K7 + 1x1 units of the encoder have no spills
-        // either way and lose 2 us with the late fetch)
-        if (pl.ntw == 3 && pl.ta == 11) return rb_by_taps<32, 3, 1, 2, ADK_RB16_PF32, false, 0>(r, pl, act, s);
-        if (pl.ntw == 3) return rb_by_taps<32, 3, 1, 2, ADK_RB16_PF32, true, 0>(r, pl, act, s);
-        return rb_by_taps<32, 4, 1, 2, 2, false, 0>(r, pl, act, s);
+    const unsigned grid = sc.grid;
+    switch (pl.arm) {                                   // (rb_choose_arm, through rb_plan)
+    case kRb32Ring:    return rb_by_taps<32, kRb32Ring, 2, 3, 1, true, 0, 3>(r, pl, grid, act, s);
+    case kRb32Few2:    return rb_by_taps<32, kRb32Few2, 2, 2, ADK_RB16_PF32, true, 0>(r, pl, grid, act, s);
+    case kRb32Three11: return rb_by_taps<32, kRb32Three11, 3, 2, ADK_RB16_PF32, false, 0>(r, pl, grid, act, s);
+    case kRb32Three:   return rb_by_taps<32, kRb32Three, 3, 2, ADK_RB16_PF32, true, 0>(r, pl, grid, act, s);
+    case kRb32Four:    return rb_by_taps<32, kRb32Four, 4, 2, 2, false, 0>(r, pl, grid, act, s);
+    case kRb64Ring:    return rb_by_taps<64, kRb64Ring, 2, 3, 1, ADK_RB16_EARLY64, 0, 3>(r, pl, grid, act, s);
+    case kRb64Few2:    return rb_by_taps<64, kRb64Few2, 2, 2, ADK_RB16_PF64, true, 0>(r, pl, grid, act, s);
+    case kRb64Three:   return rb_by_taps<64, kRb64Three, 3, 2, 2, true, 0>(r, pl, grid, act, s);
+    case kRb64Four:    return rb_by_taps<64, kRb64Four, 4, 2, 2, false, 0>(r, pl, grid, act, s);
+    case kRb128One:    return rb_by_taps<128, kRb128One, 1, 2, ADK_RB16_PF128, true, 4>(r, pl, grid, act, s);
+    case kRb128One2:   return rb_by_taps<128, kRb128One2, 1, 2, ADK_RB16_PF128, true, 4>(r, pl, grid, act, s);
+    case kRb128Two:    return rb_by_taps<128, kRb128Two, 2, 2, ADK_RB16_PF128, true, 4>(r, pl, grid, act, s);
+    default: break;
     }
-    if (pl.C == 64) {
-        if (pl.ntw == 2 && pl.spw == 1 && few) return rb_by_taps<64, 2, 1, 2, ADK_RB16_PF64, true, 0>(r, pl, act, s);
-        if (pl.ntw == 2 && pl.spw == 1) return rb_by_taps<64, 2, 1, 3, ADK_RB16_PF64, true, 0>(r, pl, act, s);
-        if (pl.ntw <= 3) return rb_by_taps<64, 3, 2, 2, 2, true, 0>(r, pl, act, s);
-        return rb_by_taps<64, 4, 2, 2, 2, false, 0>(r, pl, act, s);
-    }
-    // few streams: one stream, one tile per wave.  (Deeper weight prefetch for these one-workgroup-per-CU launches -- 8 steps at 128 channels, 4 at 32, five
-    // ring slots at 64 -- measured 1-2 % SLOWER at 1 / 8 / 32 / 64 streams, round 5: the stream of one workgroup per CU is not bound by its round trips.)
-    if (pl.ntw == 1) return rb_by_taps<128, 1, 1, 2, ADK_RB16_PF128, true, 4>(r, pl, act, s);
-    return rb_by_taps<128, 2, 2, 2, ADK_RB16_PF128, true, 4>(r, pl, act, s);
+    return ADK_ERR_STATE;
 }
 
 const char* conv_rb16_name(const ConvArgs* c, int n) {
@@ -899,3 +978,34 @@ const char* conv_rb16_name(const ConvArgs* c, int n) {
 }
 
 }  // namespace adk
+
+// The launch plan of a residual chain from its shape alone (include/audiodec_hip.h): rb_shape_ok, rb_plan and rb_schedule are the very functions
+// conv_rb16_fusable / launch_conv_rb16 go through.  No device call.
+extern "C" int adk_conv_rb16_plan(int32_t channels, int32_t taps_a, int32_t taps_b, int32_t act, const int32_t* dilations, int32_t n_convs,
+                                  int32_t batch, int32_t groups, int32_t steps, int32_t* plan) {
+    using namespace adk;
+    if (!plan || !dilations || n_convs < 2 || n_convs > kRbMaxConvs || (n_convs & 1) || batch < 1 || groups < 1 || steps < 1 || channels < 1 ||
+        taps_a < 1 || taps_b < 1)
+        return fail(ADK_ERR_ARG, "adk_conv_rb16_plan: bad argument");
+    for (int k = 0; k < n_convs; ++k)
+        if (dilations[k] < 1 || dilations[k] > (1 << 20)) return fail(ADK_ERR_ARG, "adk_conv_rb16_plan: a dilation below 1");
+    for (int i = 0; i < ADK_RB16_PLAN_WORDS; ++i) plan[i] = 0;
+    if (!rb_shape_ok(channels, act, taps_a, taps_b, n_convs)) return ADK_OK;
+    ConvArgs c[kRbMaxConvs];
+    int ksteps[kRbMaxConvs];
+    memset(c, 0, sizeof(c));
+    for (int k = 0; k < n_convs; ++k) {
+        c[k].cin_g = c[k].cout_g = channels; c[k].groups = groups; c[k].taps = (k & 1) ? taps_b : taps_a; c[k].dilation = dilations[k];
+        c[k].batch = batch; c[k].t_out = steps; c[k].ktot = c[k].taps * channels;
+        ksteps[k] = (c[k].ktot + 63) / 64 * 4;
+    }
+    RbPlan pl;
+    const bool ok = rb_plan(c, n_convs, pl);
+    if (!ok) return ADK_OK;
+    const RbSchedule sc = rb_schedule(pl, groups, n_convs, ksteps);
+    plan[0] = 1; plan[1] = pl.arm; plan[2] = pl.spw; plan[3] = pl.ntw; plan[4] = pl.n_tiles; plan[5] = pl.wr;
+    plan[6] = pl.blocks <= 128; plan[7] = sc.warm; plan[8] = sc.helpers; plan[9] = sc.helper_convs;
+    plan[10] = (int32_t)pl.lds; plan[11] = (int32_t)pl.blocks; plan[12] = (int32_t)sc.grid;
+    plan[13] = (int32_t)rb_arm_hist_capacity(pl.C, pl.arm); plan[14] = (int32_t)rb_hist_needed(pl); plan[15] = pl.hm;
+    return ADK_OK;
+}

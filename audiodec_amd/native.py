@@ -57,6 +57,7 @@ SYMBOLS = {
     "adk_set_option": (C.c_int, [C.c_char_p, _i32]),
     "adk_streamk_plan": (C.c_int, [C.c_int64, _i32, _i32, C.POINTER(C.c_int32)]),
     "adk_streamk_range_start": (C.c_int64, [C.c_int64, _i32, C.POINTER(C.c_int32), _i32]),
+    "adk_conv_rb16_plan": (C.c_int, [_i32, _i32, _i32, _i32, C.POINTER(_i32), _i32, _i32, _i32, _i32, C.POINTER(_i32)]),
     "adk_causal_conv": (C.c_int, [C.POINTER(ConvDesc), RingView, RingView, RingView, _i32, _i32, _i32, _vp]),
     "adk_causal_conv_describe": (C.c_int, [C.POINTER(ConvDesc), RingView, RingView, RingView, _i32, _i32, _i32, C.c_char_p, _i32]),
     "adk_causal_conv_time": (C.c_int, [C.POINTER(ConvDesc), RingView, RingView, RingView, _i32, _i32, _i32, _i32, _vp, C.POINTER(C.c_float)]),
@@ -197,6 +198,23 @@ FLAG_BAD_INDEX, FLAG_STREAMK_TIMEOUT, FLAG_BAD_CODE, FLAG_F16_OVERFLOW = 1, 2, 4
 def set_option(name, value):
     """Process-wide tuning / test option of the library (adk_set_option in the header)."""
     check(lib().adk_set_option(name.encode(), int(value)), "adk_set_option")
+
+
+RB16_PLAN_FIELDS = ("taken", "arm", "spw", "ntw", "n_tiles", "ring_slots", "few", "warm", "helpers", "helper_convs", "lds_bytes", "workgroups",
+                    "grid", "hist_capacity", "hist_needed", "max_hist")
+RB16_ARMS = {1: "32 ring", 2: "32 few two tiles", 3: "32 three tiles K11", 4: "32 three tiles", 5: "32 four tiles", 6: "64 ring", 7: "64 few two tiles",
+             8: "64 three tiles", 9: "64 four tiles", 10: "128 one stream one tile", 11: "128 two tiles", 12: "128 two streams one tile"}
+
+
+def conv_rb16_plan(channels, taps_a, taps_b, act, dilations, batch, groups, steps):
+    """The residual-chain kernel's launch plan for a shape (adk_conv_rb16_plan; host logic only, no GPU needed): a dict of RB16_PLAN_FIELDS,
+    `taken` False (and everything else 0) when the chain would run op by op."""
+    d = (C.c_int32 * len(dilations))(*dilations)
+    out = (C.c_int32 * len(RB16_PLAN_FIELDS))()
+    check(lib().adk_conv_rb16_plan(channels, taps_a, taps_b, act, d, len(dilations), batch, groups, steps, out), "adk_conv_rb16_plan")
+    plan = dict(zip(RB16_PLAN_FIELDS, out))
+    plan["taken"] = bool(plan["taken"])
+    return plan
 
 
 def device_flags():

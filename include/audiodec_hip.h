@@ -106,6 +106,23 @@ int adk_set_option(const char* name, int32_t value);
  * -1 on a bad argument. */
 int adk_streamk_plan(int64_t tiles, int32_t chunks, int32_t cap, int32_t* plan /* [4] */);
 int64_t adk_streamk_range_start(int64_t tiles, int32_t chunks, const int32_t* plan, int32_t r);
+/* Introspection of the residual-chain launch (csrc/conv_rb16.hip; pure host logic, no device needed): what a chain of `n_convs` convs
+ * (A_0, B_0, A_1, ...: `channels` per group in and out, taps_a / taps_b taps, activation `act` in front of every conv, dilations[k] of conv k)
+ * would run as for `batch` streams, `groups` groups and `steps` new time steps per call.  The plan comes out of the functions the launch
+ * itself goes through.  plan[0] = 1: the chain kernel takes the call (0: the ops run one by one; the other words are 0), and then
+ *   plan[1]  template arm: 1 32 ch weight ring | 2 32 ch two tiles, <= 128 workgroups | 3 32 ch three tiles K11 | 4 32 ch three tiles |
+ *            5 32 ch four tiles | 6 64 ch weight ring | 7 64 ch two tiles, <= 128 workgroups | 8 64 ch three tiles | 9 64 ch four tiles |
+ *            10 128 ch one stream, one tile | 11 128 ch two tiles | 12 128 ch two streams in one tile.  Every arm is built for the four
+ *            tap sets (LeakyReLU 11/11, 7/7, 3/3; ELU 7/1)
+ *   plan[2]  streams per workgroup        plan[3]  32-column tiles per wave        plan[4]  tiles of a full workgroup
+ *   plan[5]  slots of the LDS weight ring plan[6]  1: at most 128 workgroups       plan[7]  1: L2 warm-up touches
+ *   plan[8]  helper workgroups per XCD    plan[9]  convs whose weights they touch  plan[10] dynamic LDS bytes
+ *   plan[11] computing workgroups         plan[12] workgroups launched             plan[13] 8-channel history pieces the arm can stage
+ *   plan[14] pieces the longest history of the chain needs (<= plan[13])          plan[15] rows of that history
+ * ADK_ERR_ARG: null pointer, n_convs not 2, 4, 6 or 8, or a count below 1. */
+#define ADK_RB16_PLAN_WORDS 16
+int adk_conv_rb16_plan(int32_t channels, int32_t taps_a, int32_t taps_b, int32_t act, const int32_t* dilations, int32_t n_convs,
+                       int32_t batch, int32_t groups, int32_t steps, int32_t* plan /* [ADK_RB16_PLAN_WORDS] */);
 
 /* A view of one ring for one call. */
 typedef struct {

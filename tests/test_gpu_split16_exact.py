@@ -12,9 +12,8 @@ Part C.  What the grid cannot reach: the split's rounding of lo (a set of ties),
 absolute floor of 2^-36, not a ratio to f32), ELU's negative side through the split staging, and the f16 range boundary per family
 (65519.996 is carried, 65520.0 raises device flag bit 3).
 
-Out of scope: the residual-chain and fused-tail kernels (conv_rb16, conv_ou16, conv_oc16).  Their intermediate values leave the grid after
-one conv (a three-unit chain cannot be kept exact without contrived weights), and they are pinned bit for bit to the per-op kernels pinned
-here (tests/test_gpu_b256.py for the chains, tests/test_gpu_fused_ends.py for the fused tails)."""
+Out of scope: the fused-tail kernels (conv_ou16, conv_oc16), which tests/test_gpu_fused_ends.py holds to the per-op kernels pinned here.
+(The residual-chain kernels, conv_rb16, have their own exact model and cases: tests/chain_cases.py, tests/test_gpu_chain_variants.py.)"""
 import numpy as np
 import pytest
 import torch
