@@ -357,8 +357,10 @@ def emulate(c, ws, bs, xs, fault=None, at=1, shuffle=True):
 # ------------------------------------------------------------------------------------------------
 # the programs (GPU)
 # ------------------------------------------------------------------------------------------------
-def build_program(c, ws, bs, chain, device="cuda:0"):
-    """(HipProgram, ring of every node 0 .. n): the chain program (chain=True) or its per-op twin."""
+def build_program(c, ws, bs, chain, device="cuda:0", unit=False):
+    """(HipProgram, ring of every node 0 .. n): the chain program (chain=True) or its per-op twin.  unit=True: no chain, every op left to
+    the runner's own choice (IMPL_SPLIT16) and every unit's first conv marked fuse_next -- the fused residual unit, conv_rl16_unit<C>
+    (tests/test_gpu_fused_exact.py)."""
     from audiodec_amd import arch, native, program
     n, G, C = n_convs(c), c["groups"], c["C"]
     act = ACT_ELU if c["act"] == "ELU" else ACT_LEAKY
@@ -389,8 +391,12 @@ def build_program(c, ws, bs, chain, device="cuda:0"):
     for op in ops:
         assert op.impl == native.IMPL_SPLIT16
         op.chain, op.fuse_next = 0, 0
-        if not chain and C in (32, 64):
+        if not chain and not unit and C in (32, 64):
             op.impl = native.IMPL_SPLIT16_ROWS
+    if unit:
+        assert not chain
+        for op in ops[0::2]:
+            op.fuse_next = 1
     if chain:
         ops[0].chain = n
     return program.HipProgram(b, c["B"], c["F"], device), node_rings

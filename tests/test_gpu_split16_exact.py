@@ -12,7 +12,8 @@ Part C.  What the grid cannot reach: the split's rounding of lo (a set of ties),
 absolute floor of 2^-36, not a ratio to f32), ELU's negative side through the split staging, and the f16 range boundary per family
 (65519.996 is carried, 65520.0 raises device flag bit 3).
 
-Out of scope: the fused-tail kernels (conv_ou16, conv_oc16), which tests/test_gpu_fused_ends.py holds to the per-op kernels pinned here.
+The fused-tail kernels (conv_ou16, conv_oc16) have their own exact model through two convs and their own cases: tests/fused_cases.py,
+tests/test_fused_cases.py, tests/test_gpu_fused_exact.py (docs/design/fused_tails.md).
 (The residual-chain kernels, conv_rb16, have their own exact model and cases: tests/chain_cases.py, tests/test_gpu_chain_variants.py.)"""
 import numpy as np
 import pytest
