@@ -98,6 +98,9 @@ SYMBOLS = {
     "adk_disc_conv_grad": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float, _i32, _vp]),
     "adk_disc_prep_grad": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "adk_disc_loss_grad": (C.c_int, [_vp, _vp, _i64, _i32, C.c_double, _vp, _vp, _vp]),
+    "adk_disc_conv_wgrad_plan": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i64), C.POINTER(_i32)]),
+    "adk_disc_conv_wgrad": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+                                      C.c_float, _vp]),
     "adk_spectrogram_frames": (C.c_int64, [_i32, _i32, _i32]),
     "adk_spectrogram": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp]),
     "adk_conv2d": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,

@@ -388,6 +388,35 @@ int adk_disc_loss_grad(const float* a, const float* b, int64_t n, int32_t kind, 
                        void* stream);
 
 /*
+ * HiFi-GAN discriminator's own update (trainer/trainerGAN.py:256-294): the weight and bias gradient of the layer adk_disc_conv
+ * computes, with the same layer arguments.  Exact f32, no atomics, every element of dw and db written once, every split of a sum
+ * a function of the shape alone: bitwise reproducible.
+ * adk_disc_conv_wgrad: given dy, y [n_items][c_out][h_out][period] (y the layer's saved output, after the activation) and the
+ *   layer's input x [n_items][c_in][h_in][period], with g = o / (c_out/groups) and ci < c_in/groups:
+ *   dz[i][o][h'][j] = dy[i][o][h'][j] (act == 2 ? (y[i][o][h'][j] > 0 ? 1 : slope) : 1)       adk_disc_conv_grad's mask, also at y == 0
+ *   dw[o][ci][t]    = sum_{i,h',j} dz[i][o][h'][j] x[i][g c_in/groups + ci][h' stride - pad + t][j]   (x outside [0, h_in) is 0)
+ *   db[o]           = sum_{i,h',j} dz[i][o][h'][j]                                              db [c_out] or NULL
+ *   dw is [c_out][c_in/groups][kernel], the reference's layout (the period discriminator's Conv2d weight without its trailing 1).
+ *   y is read, and required, only when act == 2, which needs slope >= 0.  One GEMM per group (M = c_out/groups,
+ *   N = c_in/groups kernel + 1) whose reduction (i, h', j) is cut into S slices of whole 32-term steps; every (group, tile, slice)
+ *   writes an f32 partial into `workspace` [slice][c_out][c_in/groups kernel + 1], and adk_conv_wgrad's fold adds a weight's S
+ *   partials in ascending order in f64 and rounds once.  The mask is applied while dy is staged: no elementwise pass.  dw and db
+ *   are fully written (zeros for n_items == 0, which reads nothing); with db NULL the GEMM's last column is not computed.
+ *   workspace: adk_disc_conv_wgrad_plan's bytes, 4-byte aligned, any contents.
+ * adk_disc_conv_wgrad_plan: host only, no HIP call: *workspace_bytes = 4 S c_out (c_in/groups kernel + 1) and *slices = S (either
+ *   may be NULL).  adk_voc_conv_wgrad_plan's rule: tiles = groups ceil((c_out/groups) / BM) ceil((c_in/groups kernel + 1) / 128),
+ *   BM = 128 / 64 / 32 from c_out/groups >= 128 / >= 64 / below, and n = ceil(n_items h_out period / 32) steps.
+ * Every argument is checked before any HIP call (ADK_ERR_ARG): adk_disc_conv's conditions on a layer, a reduction length below
+ * 2^31 - 32, c_out (c_in/groups kernel + 1) and the x offsets of an item below 2^31, groups S <= 65535.  No allocation, no
+ * synchronisation.
+ */
+int adk_disc_conv_wgrad_plan(int32_t n_items, int32_t c_in, int32_t h_in, int32_t period, int32_t c_out, int32_t groups,
+                             int32_t kernel, int32_t stride, int32_t pad, int64_t* workspace_bytes, int32_t* slices);
+int adk_disc_conv_wgrad(const float* dy, const float* y, const float* x, float* dw, float* db, void* workspace, int32_t n_items,
+                        int32_t c_in, int32_t h_in, int32_t period, int32_t c_out, int32_t groups, int32_t kernel, int32_t stride,
+                        int32_t pad, int32_t act, float slope, void* stream);
+
+/*
  * UnivNet spectral discriminator forward (models/vocoder/modules/discriminator.py:451-640), exact f32.  The period half of the
  * UnivNet discriminator is adk_disc_conv / adk_disc_prep, the loss sums are adk_disc_loss.
  * adk_spectrogram: torchaudio.functional.spectrogram(x, pad, window, n_fft, hop, win_length, power=1.0, normalized=False)
