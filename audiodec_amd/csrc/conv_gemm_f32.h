@@ -73,11 +73,16 @@ __host__ __device__ inline int phase_taps_before(int k, int s, int r) { return (
 __host__ __device__ inline int phase_first(int pad, int s, int r) { return ((r - pad) % s + s) % s; }
 __host__ __device__ inline int phase_count(int n, int s, int first) { return first < n ? (n - first + s - 1) / s : 0; }
 
-// The check of act and impl both conv families' entry points make, f the entry point's name; `masked`: also slope >= 0 for a leaky layer (the backward, whose mask is cg_dz's).
-static inline int cg_check_act_impl(const std::string& f, int act, float slope, int impl, bool masked) {
+// The check of act (cg_check_act: also disc_wgrad.hip's, which has no impl) and of impl that both conv families' entry points make, f the
+// entry point's name; `masked`: also slope >= 0 for a leaky layer (the backward, whose mask is cg_dz's).
+static inline int cg_check_act(const std::string& f, int act, float slope, bool masked) {
     if (act != CG_ACT_NONE && act != CG_ACT_LEAKY) return fail(ADK_ERR_ARG, f + ": act must be 0 (none) or 2 (leaky)");
     if (masked && act == CG_ACT_LEAKY && !(slope >= 0.f))
         return fail(ADK_ERR_ARG, f + ": the mask is taken from the output, which needs slope >= 0");
+    return ADK_OK;
+}
+static inline int cg_check_act_impl(const std::string& f, int act, float slope, int impl, bool masked) {
+    if (const int rc = cg_check_act(f, act, slope, masked)) return rc;
     if (impl != CG_IMPL_DIRECT && impl != CG_IMPL_GEMM) return fail(ADK_ERR_ARG, f + ": impl must be 1 (direct) or 2 (gemm)");
     return ADK_OK;
 }

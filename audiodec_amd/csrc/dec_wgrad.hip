@@ -12,24 +12,23 @@
 //   g             = [i s + q < T s] dy[b][co][i s + q] + [i == 0 and q >= s] dy[b][co][q - s]       (dec_convtr_grad_kernel's operand)
 //   db[co]        = sum_{b,u} dy[b][co][u]
 //
-//   convtr_wgrad_kernel:  GEMM M = C_in, N = C_out 2s (n = co 2s + q), reduction over rho = b T + i, output m (C_out 2s) + n: the
-//                         reference's [ci][co][2s], no transpose.  x is contiguous along i: the A staging threads run along rho and
-//                         write LDS transposed, as wgrad_kernel's.  For one co, the 2s columns of a 32-deep step read the run
-//                         dy[b][co][i0 s .. (i0 + 33) s), each element twice: element (frame f, phase j < s) is column j of row f
+//   convtr_wgrad_kernel:  wgrad_gemm.h's core with M = C_in, N = C_out 2s (n = co 2s + q), reduction over rho = b T + i, output
+//                         m (C_out 2s) + n: the reference's [ci][co][2s], no transpose.  A is x, contiguous along i.  For one co,
+//                         the 2s columns of a 32-deep step read the run dy[b][co][i0 s .. (i0 + 33) s), each element twice: element (frame f, phase j < s) is column j of row f
 //                         (the first tap) and column s + j of row f - 1 (the second).  The B staging threads run along that run
 //                         -- (co, f, j) with j fastest, so a wave's loads are contiguous in time -- and scatter each element to
 //                         its two places in Bs[rho][n].  A second-tap slot is written by the element of the NEXT row whatever
 //                         item that row is in: it takes that element's value when both are in one item (else the conv's crop
 //                         leaves nothing), plus the replicate padding's share dy[b][co][j] when its own row is frame 0.  So every
 //                         slot of the tile is written exactly once per step, steps may span items, and T = 1 needs no other path.
-//                         The reduction is cut into S slices (wgrad_fold.h's rule with this GEMM's tiles); workgroup (tile, slice)
-//                         writes its f32 partial tile to the workspace [slice][m][N + 1]; wgrad_fold.h's fold adds them.
+//                         Slice blockIdx.z of S (wgrad_gemm.h's rule with this GEMM's tiles) goes to the workspace [slice][m][N + 1];
+//                         wgrad_gemm.h's fold adds them.
 //   convtr_bias_*_kernel: db is a reduction of its own on reduce_f64.h (an all-ones row of the GEMM would cost the decoder's
 //                         channel counts, all multiples of the tile, a whole row of tiles): workgroup (chunk, co) sums its share of
 //                         dy[.][co][.] in f64 -- lanes, butterfly, waves in order -- into a slab, one thread per co adds the chunks
 //                         in ascending order and rounds once.  The chunk count is a function of the shape only.
 #include "reduce_f64.h"
-#include "wgrad_fold.h"
+#include "wgrad_gemm.h"
 
 namespace adk {
 
@@ -49,49 +48,44 @@ struct ConvTrWGrad {
     const float* dy; const float* x; float* ws;     // ws [slices][c_in][nn + 1], then (8-byte aligned) double [c_out][chunks]
 };
 
-template <int WM, int WN, int TM, int TN>
-__global__ __launch_bounds__(CG_THREADS) void convtr_wgrad_kernel(ConvTrWGrad c) {
-    static_assert(WM * WN * 64 == CG_THREADS, "four waves");
-    constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
+// wgrad_gemm.h's Stage of the transposed conv: A is the activated x, B the scatter of dy described above.
+template <int BM, int BN>
+struct ConvTrWGradStage {
     static_assert(BN == DW_BN, "the host's element bound is for 128 columns");
-    constexpr int ROWS = CG_THREADS / WG_KT;                    // tile rows one pass of the 256 threads stages
-    constexpr int A_PER = BM / ROWS;
-    constexpr int LDA = (BM % 64 == 0) ? BM + 33 : BM + 1;      // = 33 mod 64, as wgrad_kernel's: the transposed stores of 32 lanes
-    constexpr int LDB = BN + 33;                                // along rho hit 32 banks, lanes 32..63 read the next row 33 banks over
-    __shared__ float As[WG_KT * LDA];
-    __shared__ float Bs[WG_KT * LDB];
-
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int wm = wid / WN, wn = wid % WN;
-    const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
+    static constexpr int A_PER = BM / WG_ROWS;
+    const int tid = threadIdx.x;
     const int kr = tid % WG_KT, row0 = tid / WG_KT;             // A: this thread's reduction offset in a step, and its first row
-    const int s = c.stride, k2 = 2 * s;
-
+    const int m0, s;
     // B: the dy elements this thread stages, e = (co, frame f of the run, phase j), j fastest.  Fixed over the steps: f, the
     // first tap's column in the tile (the second's is s further on) and the element's offset in an item at frame 0.
-    const int co0 = n0 / k2, per_co = DW_RUN * s;
-    const int n_el = (min((n0 + BN - 1) / k2, c.c_out - 1) - co0 + 1) * per_co;     // <= DW_B_PER * CG_THREADS (the host checks)
     int fr_[DW_B_PER], col[DW_B_PER], yoff[DW_B_PER];
     unsigned tap1 = 0, tap2 = 0;                                // bit i: element i's first / second tap is a slot of this tile
-#pragma unroll
-    for (int i = 0; i < DW_B_PER; ++i) {
-        const int e = tid + i * CG_THREADS;
-        const int cl = e / per_co, rem = e - cl * per_co, f = rem / s, j = rem - f * s;
-        const int n = (co0 + cl) * k2 + j - n0;
-        const bool in = e < n_el;
-        fr_[i] = in ? f : 0;
-        col[i] = in ? n : 0;
-        yoff[i] = in ? (co0 + cl) * c.ts + j : 0;
-        tap1 |= (in && f < WG_KT && n >= 0 && n < BN) ? 1u << i : 0u;
-        tap2 |= (in && f >= 1 && n + s >= 0 && n + s < BN) ? 1u << i : 0u;
-    }
-
-    // Every load is unconditional, from a clamped address (element 0: a step exists only when the operands do), so that all of a
-    // step's loads are in flight while the step before it is multiplied; what is not an operand is masked, and the activation
-    // applied, when the registers are stored to LDS.
     float ra[A_PER], rb[DW_B_PER], re[DW_B_PER];
     unsigned amask = 0, own = 0, same = 0, tgt = 0, ext = 0;
-    auto load = [&](int step) {
+
+    __device__ __forceinline__ ConvTrWGradStage(const ConvTrWGrad& c, int, int m0_, int n0) : m0(m0_), s(c.stride) {
+        const int k2 = 2 * s, co0 = n0 / k2, per_co = DW_RUN * s;
+        const int n_el = (min((n0 + BN - 1) / k2, c.c_out - 1) - co0 + 1) * per_co;     // <= DW_B_PER * CG_THREADS (the host checks)
+#pragma unroll
+        for (int i = 0; i < DW_B_PER; ++i) {
+            const int e = tid + i * CG_THREADS;
+            const int cl = e / per_co, rem = e - cl * per_co, f = rem / s, j = rem - f * s;
+            const int n = (co0 + cl) * k2 + j - n0;
+            const bool in = e < n_el;
+            fr_[i] = in ? f : 0;
+            col[i] = in ? n : 0;
+            yoff[i] = in ? (co0 + cl) * c.ts + j : 0;
+            tap1 |= (in && f < WG_KT && n >= 0 && n < BN) ? 1u << i : 0u;
+            tap2 |= (in && f >= 1 && n + s >= 0 && n + s < BN) ? 1u << i : 0u;
+        }
+    }
+    // the tile's columns past N are no element's slot: zero once
+    __device__ __forceinline__ void prepare(float* Bs, int n) {
+        for (int o = tid; o < n; o += CG_THREADS) Bs[o] = 0.f;
+        __syncthreads();
+    }
+    // clamped address: element 0 (a step exists only when the operands do)
+    __device__ __forceinline__ void load(const ConvTrWGrad& c, int step) {
         const int rho0 = step * WG_KT;
         {
             const int rho = rho0 + kr;
@@ -101,7 +95,7 @@ __global__ __launch_bounds__(CG_THREADS) void convtr_wgrad_kernel(ConvTrWGrad c)
             amask = 0;
 #pragma unroll
             for (int a = 0; a < A_PER; ++a) {
-                const int m = m0 + row0 + a * ROWS;
+                const int m = m0 + row0 + a * WG_ROWS;
                 const bool ok = live && m < c.c_in;
                 ra[a] = xb[ok ? m * c.t : 0];
                 amask |= ok ? 1u << a : 0u;
@@ -127,10 +121,10 @@ __global__ __launch_bounds__(CG_THREADS) void convtr_wgrad_kernel(ConvTrWGrad c)
             tgt |= t_live ? 1u << i : 0u;
             ext |= pad ? 1u << i : 0u;
         }
-    };
-    auto store = [&]() {
+    }
+    __device__ __forceinline__ void store(const ConvTrWGrad& c, float* As, int LDA, float* Bs, int LDB) const {
 #pragma unroll
-        for (int a = 0; a < A_PER; ++a) As[kr * LDA + row0 + a * ROWS] = (amask >> a & 1) ? in_act(ra[a], c.act, c.alpha) : 0.f;
+        for (int a = 0; a < A_PER; ++a) As[kr * LDA + row0 + a * WG_ROWS] = (amask >> a & 1) ? in_act(ra[a], c.act, c.alpha) : 0.f;
 #pragma unroll
         for (int i = 0; i < DW_B_PER; ++i) {
             if (tap1 >> i & 1) Bs[fr_[i] * LDB + col[i]] = (own >> i & 1) ? rb[i] : 0.f;
@@ -139,58 +133,14 @@ __global__ __launch_bounds__(CG_THREADS) void convtr_wgrad_kernel(ConvTrWGrad c)
                 Bs[(fr_[i] - 1) * LDB + col[i] + s] = (tgt >> i & 1) ? v : 0.f;
             }
         }
-    };
-
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int a = 0; a < TM; ++a)
-#pragma unroll
-        for (int b = 0; b < TN; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-
-    // the tile's columns past N are no element's slot: zero once
-    for (int o = tid; o < WG_KT * LDB; o += CG_THREADS) Bs[o] = 0.f;
-    __syncthreads();
-
-    const int n_steps = (c.red + WG_KT - 1) / WG_KT;
-    const int s0 = blockIdx.z * c.steps_per, s1 = min(n_steps, s0 + c.steps_per);
-    const int arow = wm * TM * 32 + (lane & 31), brow = wn * TN * 32 + (lane & 31), kh = lane >> 5;
-    if (s0 < s1) load(s0);
-    for (int st = s0; st < s1; ++st) {
-        store();
-        __syncthreads();
-        if (st + 1 < s1) load(st + 1);
-#pragma unroll
-        for (int kk = 0; kk < WG_KT; kk += 2) {
-            float av[TM], bv[TN];
-#pragma unroll
-            for (int a = 0; a < TM; ++a) av[a] = As[(kk + kh) * LDA + arow + a * 32];
-#pragma unroll
-            for (int b = 0; b < TN; ++b) bv[b] = Bs[(kk + kh) * LDB + brow + b * 32];
-#pragma unroll
-            for (int a = 0; a < TM; ++a)
-#pragma unroll
-                for (int b = 0; b < TN; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[a], bv[b], acc[a][b], 0, 0, 0);
-        }
-        __syncthreads();
     }
+};
 
-    // C/D map col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5); the partial tile goes to ws[slice][m][n]
-    const int nc = c.nn + 1;
-    float* __restrict__ wsz = c.ws + (size_t)blockIdx.z * c.c_in * nc;
-#pragma unroll
-    for (int b = 0; b < TN; ++b) {
-        const int n = n0 + wn * TN * 32 + b * 32 + (lane & 31);
-        if (n >= c.nn) continue;
-#pragma unroll
-        for (int a = 0; a < TM; ++a)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm * TM * 32 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                if (m < c.c_in) wsz[(size_t)m * nc + n] = acc[a][b][r];
-            }
-    }
+template <int WM, int WN, int TM, int TN>
+__global__ __launch_bounds__(CG_THREADS) void convtr_wgrad_kernel(ConvTrWGrad c) {
+    const int slice = blockIdx.z;
+    ConvTrWGradStage<WM * TM * 32, WN * TN * 32> stage(c, 0, blockIdx.y * (WM * TM * 32), blockIdx.x * (WN * TN * 32));
+    wgrad_gemm<WM, WN, TM, TN>(stage, c, c.red, c.steps_per, slice, c.c_in, c.nn, c.ws + (size_t)slice * c.c_in * (c.nn + 1), c.nn + 1);
 }
 
 // Workgroup (chunk, co): the (b, u) pairs [chunk * chunk_len, + chunk_len) of channel co, u fastest.
@@ -219,9 +169,7 @@ static int convtr_wgrad_plan(const std::string& f, int n_items, int c_in, int t,
                              float alpha, ConvTrWGrad& g, long long& ws_floats, long long& ws_bytes) {
     if (n_items < 0 || c_in <= 0 || t <= 0 || c_out <= 0 || kernel <= 0 || stride <= 0)
         return fail(ADK_ERR_ARG, f + ": need n_items >= 0, c_in, t, c_out, kernel, stride > 0");
-    if (act < IN_ACT_NONE || act > max_act)
-        return fail(ADK_ERR_ARG, f + (max_act == IN_ACT_ELU ? ": act must be 0 (none) or 1 (ELU)" : ": act must be 0 (none), 1 (ELU) or 2 (LeakyReLU)"));
-    if (act != IN_ACT_NONE && !(alpha == alpha)) return fail(ADK_ERR_ARG, f + ": alpha is NaN");
+    if (const int rc = wgrad_check_in_act(f, act, max_act, alpha)) return rc;
     const long long ts = (long long)t * stride, nn = 2LL * c_out * stride, red = (long long)n_items * t;
     // a tile's columns touch at most (BN - 1) / 2s + 2 channels, each with 33 s elements a step: they must fit the staging registers
     const long long el = stride <= DW_BN ? ((DW_BN - 1) / (2LL * stride) + 2) * DW_RUN * stride : (1LL << 40);
@@ -230,10 +178,8 @@ static int convtr_wgrad_plan(const std::string& f, int n_items, int c_in, int t,
         c_in * (nn + 1) >= (1LL << 31) || (c_in + 31) / 32 > 65535 || c_out > 65535)
         return fail(ADK_ERR_ARG, f + ": layer too large");
     if ((long long)kernel != 2LL * stride) return fail(ADK_ERR_ARG, f + ": kernel must be 2 * stride");
-    const int bm = c_in >= 128 ? 128 : c_in >= 64 ? 64 : 32;
-    const long long tiles = (long long)((c_in + bm - 1) / bm) * ((nn + DW_BN - 1) / DW_BN);
     long long steps_per = 1, slices = 1;
-    wgrad_slices(tiles, (red + WG_KT - 1) / WG_KT, steps_per, slices);
+    wgrad_slices(wgrad_tiles(1, c_in, nn), (red + WG_KT - 1) / WG_KT, steps_per, slices);
     const long long total = n_items * ts;
     const long long want = std::max<long long>(1, std::min<long long>(DW_BIAS_MAX_CHUNKS, (total + DW_BIAS_CHUNK - 1) / DW_BIAS_CHUNK));
     const long long chunk_len = std::max<long long>(1, (total + want - 1) / want);
@@ -259,10 +205,7 @@ static int convtr_wgrad(const std::string& f, int max_act, const float* dy, cons
     c.dy = dy; c.x = x; c.ws = static_cast<float*>(workspace);
     hipStream_t s = static_cast<hipStream_t>(stream);
     DeviceGuard guard(device_of(dw));
-    const unsigned nx = (unsigned)((c.nn + DW_BN - 1) / DW_BN);
-    if (c_in >= 128) hipLaunchKernelGGL((convtr_wgrad_kernel<2, 2, 2, 2>), dim3(nx, (c_in + 127) / 128, c.slices), dim3(CG_THREADS), 0, s, c);
-    else if (c_in >= 64) hipLaunchKernelGGL((convtr_wgrad_kernel<2, 2, 1, 2>), dim3(nx, (c_in + 63) / 64, c.slices), dim3(CG_THREADS), 0, s, c);
-    else hipLaunchKernelGGL((convtr_wgrad_kernel<1, 4, 1, 1>), dim3(nx, (c_in + 31) / 32, c.slices), dim3(CG_THREADS), 0, s, c);
+    WGRAD_LAUNCH(convtr_wgrad_kernel, c, c_in, (unsigned)((c.nn + DW_BN - 1) / DW_BN), c.slices, s);
     ADK_HIP_CHECK(hipGetLastError());
     launch_wgrad_fold(c.ws, dw, nullptr, (int)c_in, c.nn, c.slices, s);
     ADK_HIP_CHECK(hipGetLastError());

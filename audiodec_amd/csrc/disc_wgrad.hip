@@ -9,18 +9,15 @@
 //   dW[o][ci][t]    = sum_{i,h',j} dz[i][o][h'][j] x[i][g C_in/G + ci][h' s - pad + t][j]              (x outside [0, h_in) is 0)
 //   db[o]           = sum_{i,h',j} dz[i][o][h'][j]
 //
-//   disc_wgrad_kernel:  enc_grad.hip's wgrad_kernel on this addressing.  One GEMM per group: M = C_out/G, N = (C_in/G) k + 1
-//                       (n = ci k + t; the last column's operand is 1: db, left out when db is not asked for), reduction over
-//                       rho = (i h_out + h') P + j.  dy and y are contiguous along rho inside an item, so the staging threads run
-//                       along rho and write LDS transposed to the MFMA's [rho][m] / [rho][n].  The mask is applied to the A
-//                       operand when the registers are stored to LDS (two loads per element, as DiscGradSrc::tap; no elementwise
-//                       pass of its own).  A B element is an operand when 0 <= h' s - pad + t < h_in: a two-sided test, unlike the
-//                       causal kernel's.  Rows of x the forward never reached (the tail when h_in + 2 pad - k is no multiple of s)
-//                       are never addressed.  The reduction is cut into S slices of whole 32-deep steps (disc_wgrad_plan);
-//                       blockIdx.z = g S + slice; workgroup (group, tile, slice) writes its f32 partial tile to the workspace
-//                       [slice][g C_out/G + m][n]: the layout of dW itself.
-//   wgrad_fold_kernel:  (wgrad_fold.h) the S partials in ascending slice order in f64, rounded once, stored as dW [co][ci][k] or db.
-#include "wgrad_fold.h"
+//   disc_wgrad_kernel:  wgrad_gemm.h's core, one GEMM per group: M = C_out/G, N = (C_in/G) k + 1 (n = ci k + t; the last column's
+//                       operand is 1: db, left out when db is not asked for), reduction over rho = (i h_out + h') P + j, along which
+//                       dy and y are contiguous inside an item.  The mask is applied to the A operand when the registers are stored
+//                       to LDS (two loads per element, as DiscGradSrc::tap; no elementwise pass of its own).  A B element is an
+//                       operand when 0 <= h' s - pad + t < h_in: a two-sided test, unlike the causal kernel's.  Rows of x the
+//                       forward never reached (the tail when h_in + 2 pad - k is no multiple of s) are never addressed.
+//                       blockIdx.z = g S + slice (disc_wgrad_plan); the workspace is [slice][g C_out/G + m][n]: the layout of dW
+//                       itself ([co][ci][k]), which wgrad_gemm.h's fold then writes.
+#include "wgrad_gemm.h"
 
 namespace adk {
 
@@ -39,45 +36,35 @@ struct DiscWGrad {
 
 constexpr int DW_NO_TAP = -0x40000000;              // t - pad of a column that reads no x: its row test fails for every h'
 
-template <int WM, int WN, int TM, int TN>
-__global__ __launch_bounds__(CG_THREADS) void disc_wgrad_kernel(DiscWGrad c) {
-    static_assert(WM * WN * 64 == CG_THREADS, "four waves");
-    constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
-    constexpr int ROWS = CG_THREADS / WG_KT;                    // tile rows one pass of the 256 threads stages
-    constexpr int A_PER = BM / ROWS, B_PER = BN / ROWS;
-    constexpr int LDA = (BM % 64 == 0) ? BM + 33 : BM + 1;      // as wgrad_kernel's: the transposed stores of 32 lanes along rho
-    constexpr int LDB = (BN % 64 == 0) ? BN + 33 : BN + 1;      // hit 32 banks, and lanes 32..63 read the next row 33 banks over
-    __shared__ float As[WG_KT * LDA];
-    __shared__ float Bs[WG_KT * LDB];
-
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int wm = wid / WN, wn = wid % WN;
-    const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
-    const int kr = tid % WG_KT, row0 = tid / WG_KT;             // this thread's reduction offset in a step, and its first row
-    const int grp = blockIdx.z / c.slices, slice = blockIdx.z - grp * c.slices;
-    const int row_g = grp * c.cout_g, ch_g = grp * c.cin_g;     // the group's first dy / workspace row and first x channel
-    const bool leaky = c.act == CG_ACT_LEAKY;
-
-    // the columns this thread stages: x offset of tap (ci, t) inside an item at h' = 0, j = 0, and the row t - pad it starts from
-    int xoff[B_PER], trow[B_PER];
+// wgrad_gemm.h's Stage of the discriminator's conv: A is dz (dy through y's mask), B is x at tap (ci, t), or 1 in db's column.
+template <int BM, int BN>
+struct DiscWGradStage {
+    static constexpr int A_PER = BM / WG_ROWS, B_PER = BN / WG_ROWS;
+    const int kr = threadIdx.x % WG_KT, row0 = threadIdx.x / WG_KT;    // this thread's reduction offset in a step, and its first row
+    const int m0, row_g;                                        // the tile's first row in the group, the group's first dy row
+    const bool leaky;
+    int xoff[B_PER], trow[B_PER];                               // per column: x offset of tap (ci, t) in an item at h' = 0, j = 0; its row t - pad
     unsigned bias_col = 0;                                      // bit i: this thread's column i is db's
-#pragma unroll
-    for (int i = 0; i < B_PER; ++i) {
-        const int n = n0 + row0 + i * ROWS;
-        const bool tap = n < c.ck;                              // the bias column and columns past it read no x
-        const int ci = n / c.ksz, tr = n - ci * c.ksz - c.pad;
-        xoff[i] = tap ? (ch_g + ci) * c.hp_in + tr * c.period : 0;
-        trow[i] = tap ? tr : DW_NO_TAP;
-        bias_col |= (n == c.ck && n < c.nc_live) ? 1u << i : 0u;
-    }
-
-    // Every load is unconditional, from a clamped address (element 0 of the tensor: a step exists only when the operands do), so
-    // that all of a step's loads are in flight while the step before it is multiplied; what is not an operand is zeroed, and the
-    // mask applied, when the registers are stored to LDS.
     float ra[A_PER], ry[A_PER], rb[B_PER];
     unsigned amask = 0, bmask = 0;
     bool live = false;
-    auto load = [&](int step) {
+
+    __device__ __forceinline__ DiscWGradStage(const DiscWGrad& c, int grp, int m0_, int n0)
+        : m0(m0_), row_g(grp * c.cout_g), leaky(c.act == CG_ACT_LEAKY) {
+        const int ch_g = grp * c.cin_g;                         // the group's first x channel
+#pragma unroll
+        for (int i = 0; i < B_PER; ++i) {
+            const int n = n0 + row0 + i * WG_ROWS;
+            const bool tap = n < c.ck;                          // the bias column and columns past it read no x
+            const int ci = n / c.ksz, tr = n - ci * c.ksz - c.pad;
+            xoff[i] = tap ? (ch_g + ci) * c.hp_in + tr * c.period : 0;
+            trow[i] = tap ? tr : DW_NO_TAP;
+            bias_col |= (n == c.ck && n < c.nc_live) ? 1u << i : 0u;
+        }
+    }
+    __device__ __forceinline__ void prepare(float*, int) {}
+    // clamped address: element 0 of the tensor (a step exists only when the operands do)
+    __device__ __forceinline__ void load(const DiscWGrad& c, int step) {
         const int rho = step * WG_KT + kr;
         live = rho < c.red;
         const int item = live ? rho / c.hp_out : 0, rem = live ? rho - item * c.hp_out : 0;
@@ -90,7 +77,7 @@ __global__ __launch_bounds__(CG_THREADS) void disc_wgrad_kernel(DiscWGrad c) {
         amask = bmask = 0;
 #pragma unroll
         for (int i = 0; i < A_PER; ++i) {
-            const int m = m0 + row0 + i * ROWS;
+            const int m = m0 + row0 + i * WG_ROWS;
             const bool ok = live && m < c.cout_g;
             const long long off = ok ? (long long)(row_g + m) * c.hp_out : -(long long)rem;      // clamped: the item's element 0
             ra[i] = dyb[off];
@@ -103,71 +90,32 @@ __global__ __launch_bounds__(CG_THREADS) void disc_wgrad_kernel(DiscWGrad c) {
             rb[i] = xb[ok ? xoff[i] + q : 0];
             bmask |= ok ? 1u << i : 0u;
         }
-    };
-    auto store = [&]() {
+    }
+    __device__ __forceinline__ void store(const DiscWGrad& c, float* As, int LDA, float* Bs, int LDB) const {
 #pragma unroll
         for (int i = 0; i < A_PER; ++i) {
             const float dz = (leaky && !(ry[i] > 0.f)) ? ra[i] * c.slope : ra[i];
-            As[kr * LDA + row0 + i * ROWS] = (amask >> i & 1) ? dz : 0.f;
+            As[kr * LDA + row0 + i * WG_ROWS] = (amask >> i & 1) ? dz : 0.f;
         }
 #pragma unroll
         for (int i = 0; i < B_PER; ++i) {
             const float one = (live && (bias_col >> i & 1)) ? 1.f : 0.f;
-            Bs[kr * LDB + row0 + i * ROWS] = (bmask >> i & 1) ? rb[i] : one;
+            Bs[kr * LDB + row0 + i * WG_ROWS] = (bmask >> i & 1) ? rb[i] : one;
         }
-    };
-
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int a = 0; a < TM; ++a)
-#pragma unroll
-        for (int b = 0; b < TN; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-
-    const int n_steps = (c.red + WG_KT - 1) / WG_KT;
-    const int s0 = slice * c.steps_per, s1 = min(n_steps, s0 + c.steps_per);
-    const int arow = wm * TM * 32 + (lane & 31), brow = wn * TN * 32 + (lane & 31), kh = lane >> 5;
-    if (s0 < s1) load(s0);
-    for (int st = s0; st < s1; ++st) {
-        store();
-        __syncthreads();
-        if (st + 1 < s1) load(st + 1);
-#pragma unroll
-        for (int kk = 0; kk < WG_KT; kk += 2) {
-            float av[TM], bv[TN];
-#pragma unroll
-            for (int a = 0; a < TM; ++a) av[a] = As[(kk + kh) * LDA + arow + a * 32];
-#pragma unroll
-            for (int b = 0; b < TN; ++b) bv[b] = Bs[(kk + kh) * LDB + brow + b * 32];
-#pragma unroll
-            for (int a = 0; a < TM; ++a)
-#pragma unroll
-                for (int b = 0; b < TN; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[a], bv[b], acc[a][b], 0, 0, 0);
-        }
-        __syncthreads();
     }
+};
 
-    // C/D map col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5); the partial tile goes to ws[slice][row_g + m][n]
-    const int nc = c.ck + 1;
-    float* __restrict__ wsz = c.ws + ((size_t)slice * c.c_out + row_g) * nc;
-#pragma unroll
-    for (int b = 0; b < TN; ++b) {
-        const int n = n0 + wn * TN * 32 + b * 32 + (lane & 31);
-        if (n >= c.nc_live) continue;
-#pragma unroll
-        for (int a = 0; a < TM; ++a)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm * TM * 32 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                if (m < c.cout_g) wsz[(size_t)m * nc + n] = acc[a][b][r];
-            }
-    }
+template <int WM, int WN, int TM, int TN>
+__global__ __launch_bounds__(CG_THREADS) void disc_wgrad_kernel(DiscWGrad c) {
+    const int grp = blockIdx.z / c.slices, slice = blockIdx.z - grp * c.slices;
+    DiscWGradStage<WM * TM * 32, WN * TN * 32> stage(c, grp, blockIdx.y * (WM * TM * 32), blockIdx.x * (WN * TN * 32));
+    wgrad_gemm<WM, WN, TM, TN>(stage, c, c.red, c.steps_per, slice, c.cout_g, c.nc_live,
+                               c.ws + ((size_t)slice * c.c_out + grp * c.cout_g) * (c.ck + 1), c.ck + 1);
 }
 
 // ---- host ----
 // disc_geometry's conditions on a layer (disc.hip), under this entry point's name, then the 32-bit limits of the kernel's
-// indices and the slice rule: wgrad_fold.h's wgrad_slices with the tiles of all groups.
+// indices and the slice rule: wgrad_gemm.h's wgrad_slices with the tiles of all groups.
 static int disc_wgrad_plan(const std::string& f, int n_items, int c_in, int h_in, int period, int c_out, int groups, int kernel,
                            int stride, int pad, DiscWGrad& g, long long& ws_bytes) {
     if (n_items < 0 || c_in <= 0 || h_in <= 0 || period <= 0 || c_out <= 0 || groups <= 0 || kernel <= 0 || stride <= 0 || pad < 0)
@@ -183,11 +131,8 @@ static int disc_wgrad_plan(const std::string& f, int n_items, int c_in, int h_in
         ((long long)h_in + 2LL * pad) * period >= (1LL << 31) || red >= (1LL << 31) - WG_KT || c_out * (ck + 1) >= (1LL << 31) ||
         (cout_g + 31) / 32 > 65535)
         return fail(ADK_ERR_ARG, f + ": layer too large");
-    const int bm = cout_g >= 128 ? 128 : cout_g >= 64 ? 64 : 32;
-    const long long tiles = (long long)groups * ((cout_g + bm - 1) / bm) * ((ck + 1 + 127) / 128);
-    const long long n_steps = (red + WG_KT - 1) / WG_KT;
     long long steps_per = 1, slices = 1;
-    wgrad_slices(tiles, n_steps, steps_per, slices);
+    wgrad_slices(wgrad_tiles(groups, cout_g, ck + 1), (red + WG_KT - 1) / WG_KT, steps_per, slices);
     if (groups * slices > 65535) return fail(ADK_ERR_ARG, f + ": layer too large (groups * slices is the grid's z)");
     g.n_items = n_items; g.c_in = c_in; g.h_in = h_in; g.period = period; g.c_out = c_out; g.groups = groups; g.ksz = kernel;
     g.stride = stride; g.pad = pad; g.h_out = (int)h_out; g.cin_g = cin_g; g.cout_g = cout_g; g.hp_in = (int)hp_in;
@@ -220,9 +165,8 @@ extern "C" int adk_disc_conv_wgrad(const float* dy, const float* y, const float*
     long long bytes = 0;
     int rc = disc_wgrad_plan(f, n_items, c_in, h_in, period, c_out, groups, kernel, stride, pad, c, bytes);
     if (rc != ADK_OK) return rc;
-    if (act != CG_ACT_NONE && act != CG_ACT_LEAKY) return fail(ADK_ERR_ARG, f + ": act must be 0 (none) or 2 (leaky)");
-    if (act == CG_ACT_LEAKY && !(slope >= 0.f))
-        return fail(ADK_ERR_ARG, f + ": the mask is taken from the output, which needs slope >= 0");
+    rc = cg_check_act(f, act, slope, true);
+    if (rc != ADK_OK) return rc;
     rc = check_pointers(f, "dy/y/x/dw/db/workspace", !dw || !workspace || (n_items > 0 && (!dy || !x || (act == CG_ACT_LEAKY && !y))),
                         {dy, y, x, dw, db, workspace});
     if (rc != ADK_OK) return rc;
@@ -231,11 +175,7 @@ extern "C" int adk_disc_conv_wgrad(const float* dy, const float* y, const float*
     c.nc_live = db ? c.ck + 1 : c.ck;                          // without db its column is not computed
     hipStream_t s = static_cast<hipStream_t>(stream);
     DeviceGuard guard(device_of(dw));
-    const unsigned nx = (unsigned)((c.nc_live + 127) / 128), nz = (unsigned)(groups * c.slices);
-    const int m = c.cout_g;
-    if (m >= 128) hipLaunchKernelGGL((disc_wgrad_kernel<2, 2, 2, 2>), dim3(nx, (m + 127) / 128, nz), dim3(CG_THREADS), 0, s, c);
-    else if (m >= 64) hipLaunchKernelGGL((disc_wgrad_kernel<2, 2, 1, 2>), dim3(nx, (m + 63) / 64, nz), dim3(CG_THREADS), 0, s, c);
-    else hipLaunchKernelGGL((disc_wgrad_kernel<1, 4, 1, 1>), dim3(nx, (m + 31) / 32, nz), dim3(CG_THREADS), 0, s, c);
+    WGRAD_LAUNCH(disc_wgrad_kernel, c, c.cout_g, (unsigned)((c.nc_live + 127) / 128), (unsigned)(groups * c.slices), s);
     ADK_HIP_CHECK(hipGetLastError());
     launch_wgrad_fold(c.ws, dw, db, (int)c_out, c.ck, c.slices, s);
     ADK_HIP_CHECK(hipGetLastError());

@@ -17,16 +17,13 @@
 //                          (kk = 2 co + tap), N = B count_r, count_r the v < T of phase r; W re-packed to [r][kk][ci].  A phase's
 //                          stores are strided by s.  No structural zero is multiplied.
 //   wgrad_kernel:          dW[co][ci][j] = sum_{b,u} dy[b][co][u] a(x[b][g C_in/G + ci][u s - (k-1-j) d]),  db[co] = sum_{b,u} dy[b][co][u]
-//                          for co of group g = co / (C_out/G) and ci < C_in/G.  One GEMM per group: M = C_out/G, N = (C_in/G) k + 1
-//                          (n = ci k + j; the last column's tap is 1: db, left out when db is not asked for, which saves the 1x1
-//                          convs of 2^n channels a whole column tile), reduction over rho = b T_out + u.  dy and x are contiguous
-//                          along u, so the staging threads run along rho and write LDS transposed to the MFMA's [rho][m] /
-//                          [rho][n].  The reduction is cut into S slices of whole 32-deep steps (wgrad_plan: a function of the shape
-//                          only); blockIdx.z = g S + slice; workgroup (group, tile, slice) writes its f32 partial tile to the
-//                          workspace [slice][g C_out/G + m][n]: rows of all groups side by side, the layout of dW itself.
-//   wgrad_fold_kernel:     (wgrad_fold.h, shared with dec_wgrad.hip) one thread per (m, n): the S partials in ascending slice
-//                          order in f64, rounded once, stored as dW [co][ci][k] (the reference's layout: m (C_in k) + n) or db[m].
-#include "wgrad_fold.h"
+//                          for co of group g = co / (C_out/G) and ci < C_in/G.  wgrad_gemm.h's core, one GEMM per group: M = C_out/G,
+//                          N = (C_in/G) k + 1 (n = ci k + j; the last column's tap is 1: db, left out when db is not asked for, which
+//                          saves the 1x1 convs of 2^n channels a whole column tile), reduction over rho = b T_out + u, along which
+//                          dy and x are contiguous.  blockIdx.z = g S + slice (wgrad_plan); the workspace is [slice][g C_out/G + m][n]:
+//                          rows of all groups side by side, the layout of dW itself (the reference's: m (C_in k) + n), which
+//                          wgrad_gemm.h's fold then writes.
+#include "wgrad_gemm.h"
 
 namespace adk {
 
@@ -130,44 +127,33 @@ struct WGrad {
     const float* dy; const float* x; float* ws;     // ws [slices][c_out][ck + 1]
 };                                                  // the grid's z is groups * slices
 
-template <int WM, int WN, int TM, int TN>
-__global__ __launch_bounds__(CG_THREADS) void wgrad_kernel(WGrad c) {
-    static_assert(WM * WN * 64 == CG_THREADS, "four waves");
-    constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
-    constexpr int ROWS = CG_THREADS / WG_KT;                    // tile rows one pass of the 256 threads stages
-    constexpr int A_PER = BM / ROWS, B_PER = BN / ROWS;
-    constexpr int LDA = (BM % 64 == 0) ? BM + 33 : BM + 1;      // = 33 mod 64: the transposed stores of 32 lanes along rho hit 32
-    constexpr int LDB = (BN % 64 == 0) ? BN + 33 : BN + 1;      // banks, and lanes 32..63 read the next row 33 banks over
-    __shared__ float As[WG_KT * LDA];
-    __shared__ float Bs[WG_KT * LDB];
-
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int wm = wid / WN, wn = wid % WN;
-    const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
-    const int kr = tid % WG_KT, row0 = tid / WG_KT;             // this thread's reduction offset in a step, and its first row
-    const int grp = blockIdx.z / c.slices, slice = blockIdx.z - grp * c.slices;
-    const int row_g = grp * c.cout_g, ch_g = grp * c.cin_g;     // the group's first dy / workspace row and first x channel
-
-    // the columns this thread stages: x offset of tap (ci, j) inside an item, and the u s it needs at least
-    int xoff[B_PER], need[B_PER];
+// wgrad_gemm.h's Stage of the causal conv: A is dy (rows of the group), B the activated x at tap (ci, j), or 1 in db's column.
+template <int BM, int BN>
+struct WGradStage {
+    static constexpr int A_PER = BM / WG_ROWS, B_PER = BN / WG_ROWS;
+    const int kr = threadIdx.x % WG_KT, row0 = threadIdx.x / WG_KT;    // this thread's reduction offset in a step, and its first row
+    const int m0, row_g;                                        // the tile's first row in the group, the group's first dy row
+    int xoff[B_PER], need[B_PER];                               // per column: x offset of tap (ci, j) inside an item, the u s it needs at least
     unsigned bias_col = 0;                                      // bit i: this thread's column i is db's
-#pragma unroll
-    for (int i = 0; i < B_PER; ++i) {
-        const int n = n0 + row0 + i * ROWS;
-        const bool tap = n < c.ck;                              // the bias column and columns past it read no x
-        const int ci = n / c.ksz, back = (c.ksz - 1 - (n - ci * c.ksz)) * c.dil;
-        xoff[i] = tap ? (ch_g + ci) * c.t - back : 0;
-        need[i] = tap ? back : 0x7fffffff;
-        bias_col |= (n == c.ck && n < c.nc_live) ? 1u << i : 0u;
-    }
-
-    // Every load is unconditional, from a clamped address (element 0 of the item: a step exists only when the operands do), so
-    // that all of a step's loads are in flight while the step before it is multiplied; what is not an operand is masked, and
-    // the activation applied, when the registers are stored to LDS.
     float ra[A_PER], rb[B_PER];
     unsigned amask = 0, bmask = 0;
     bool live = false;
-    auto load = [&](int step) {
+
+    __device__ __forceinline__ WGradStage(const WGrad& c, int grp, int m0_, int n0) : m0(m0_), row_g(grp * c.cout_g) {
+        const int ch_g = grp * c.cin_g;                         // the group's first x channel
+#pragma unroll
+        for (int i = 0; i < B_PER; ++i) {
+            const int n = n0 + row0 + i * WG_ROWS;
+            const bool tap = n < c.ck;                          // the bias column and columns past it read no x
+            const int ci = n / c.ksz, back = (c.ksz - 1 - (n - ci * c.ksz)) * c.dil;
+            xoff[i] = tap ? (ch_g + ci) * c.t - back : 0;
+            need[i] = tap ? back : 0x7fffffff;
+            bias_col |= (n == c.ck && n < c.nc_live) ? 1u << i : 0u;
+        }
+    }
+    __device__ __forceinline__ void prepare(float*, int) {}
+    // clamped address: element 0 of the item (a step exists only when the operands do)
+    __device__ __forceinline__ void load(const WGrad& c, int step) {
         const int rho = step * WG_KT + kr;
         live = rho < c.red;
         const int item = live ? rho / c.t_out : 0, u = live ? rho - item * c.t_out : 0;
@@ -177,7 +163,7 @@ __global__ __launch_bounds__(CG_THREADS) void wgrad_kernel(WGrad c) {
         amask = bmask = 0;
 #pragma unroll
         for (int i = 0; i < A_PER; ++i) {
-            const int m = m0 + row0 + i * ROWS;
+            const int m = m0 + row0 + i * WG_ROWS;
             const bool ok = live && m < c.cout_g;
             ra[i] = dyb[ok ? (long long)(row_g + m) * c.t_out : 0];
             amask |= ok ? 1u << i : 0u;
@@ -188,63 +174,24 @@ __global__ __launch_bounds__(CG_THREADS) void wgrad_kernel(WGrad c) {
             rb[i] = xb[ok ? xoff[i] + p : 0];
             bmask |= ok ? 1u << i : 0u;
         }
-    };
-    auto store = [&]() {
+    }
+    __device__ __forceinline__ void store(const WGrad& c, float* As, int LDA, float* Bs, int LDB) const {
 #pragma unroll
-        for (int i = 0; i < A_PER; ++i) As[kr * LDA + row0 + i * ROWS] = (amask >> i & 1) ? ra[i] : 0.f;
+        for (int i = 0; i < A_PER; ++i) As[kr * LDA + row0 + i * WG_ROWS] = (amask >> i & 1) ? ra[i] : 0.f;
 #pragma unroll
         for (int i = 0; i < B_PER; ++i) {
             const float one = (live && (bias_col >> i & 1)) ? 1.f : 0.f;
-            Bs[kr * LDB + row0 + i * ROWS] = (bmask >> i & 1) ? in_act(rb[i], c.act, c.alpha) : one;
+            Bs[kr * LDB + row0 + i * WG_ROWS] = (bmask >> i & 1) ? in_act(rb[i], c.act, c.alpha) : one;
         }
-    };
-
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int a = 0; a < TM; ++a)
-#pragma unroll
-        for (int b = 0; b < TN; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-
-    const int n_steps = (c.red + WG_KT - 1) / WG_KT;
-    const int s0 = slice * c.steps_per, s1 = min(n_steps, s0 + c.steps_per);
-    const int arow = wm * TM * 32 + (lane & 31), brow = wn * TN * 32 + (lane & 31), kh = lane >> 5;
-    if (s0 < s1) load(s0);
-    for (int st = s0; st < s1; ++st) {
-        store();
-        __syncthreads();
-        if (st + 1 < s1) load(st + 1);
-#pragma unroll
-        for (int kk = 0; kk < WG_KT; kk += 2) {
-            float av[TM], bv[TN];
-#pragma unroll
-            for (int a = 0; a < TM; ++a) av[a] = As[(kk + kh) * LDA + arow + a * 32];
-#pragma unroll
-            for (int b = 0; b < TN; ++b) bv[b] = Bs[(kk + kh) * LDB + brow + b * 32];
-#pragma unroll
-            for (int a = 0; a < TM; ++a)
-#pragma unroll
-                for (int b = 0; b < TN; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[a], bv[b], acc[a][b], 0, 0, 0);
-        }
-        __syncthreads();
     }
+};
 
-    // C/D map col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5); the partial tile goes to ws[slice][row_g + m][n]
-    const int nc = c.ck + 1;
-    float* __restrict__ wsz = c.ws + ((size_t)slice * c.c_out + row_g) * nc;
-#pragma unroll
-    for (int b = 0; b < TN; ++b) {
-        const int n = n0 + wn * TN * 32 + b * 32 + (lane & 31);
-        if (n >= c.nc_live) continue;
-#pragma unroll
-        for (int a = 0; a < TM; ++a)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm * TM * 32 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                if (m < c.cout_g) wsz[(size_t)m * nc + n] = acc[a][b][r];
-            }
-    }
+template <int WM, int WN, int TM, int TN>
+__global__ __launch_bounds__(CG_THREADS) void wgrad_kernel(WGrad c) {
+    const int grp = blockIdx.z / c.slices, slice = blockIdx.z - grp * c.slices;
+    WGradStage<WM * TM * 32, WN * TN * 32> stage(c, grp, blockIdx.y * (WM * TM * 32), blockIdx.x * (WN * TN * 32));
+    wgrad_gemm<WM, WN, TM, TN>(stage, c, c.red, c.steps_per, slice, c.cout_g, c.nc_live,
+                               c.ws + ((size_t)slice * c.c_out + grp * c.cout_g) * (c.ck + 1), c.ck + 1);
 }
 
 // ---- host ----
@@ -269,7 +216,7 @@ static int enc_down_geometry(const std::string& f, int n_items, int c_in, int t,
         else hipLaunchKernelGGL((kernel<1, 4, 1, 1>), dim3(nx128, ((m) + 31) / 32, phases), dim3(CG_THREADS), 0, s, c);  \
     } while (0)
 
-// The weight gradient's checks and geometry; the slice rule is wgrad_fold.h's wgrad_slices with the tiles of all groups.  max_act
+// The weight gradient's checks and geometry; the slice rule is wgrad_gemm.h's wgrad_slices with the tiles of all groups.  max_act
 // is the largest act the entry point takes: IN_ACT_ELU for adk_conv_wgrad, IN_ACT_LEAKY for adk_voc_conv_wgrad.
 static int wgrad_plan(const std::string& f, int n_items, int c_in, int t, int c_out, int kernel, int dil, int stride, int groups,
                       int act, int max_act, float alpha, WGrad& g, long long& ws_bytes) {
@@ -277,9 +224,7 @@ static int wgrad_plan(const std::string& f, int n_items, int c_in, int t, int c_
         return fail(ADK_ERR_ARG, f + ": need n_items >= 0, c_in, t, c_out, kernel, dilation, stride > 0");
     if (groups < 1 || c_in % groups || c_out % groups)
         return fail(ADK_ERR_ARG, f + ": need groups >= 1 that divides c_in and c_out");
-    if (act < IN_ACT_NONE || act > max_act)
-        return fail(ADK_ERR_ARG, f + (max_act == IN_ACT_ELU ? ": act must be 0 (none) or 1 (ELU)" : ": act must be 0 (none), 1 (ELU) or 2 (LeakyReLU)"));
-    if (act != IN_ACT_NONE && !(alpha == alpha)) return fail(ADK_ERR_ARG, f + ": alpha is NaN");
+    if (const int rc = wgrad_check_in_act(f, act, max_act, alpha)) return rc;
     const int t_out = (t - 1) / stride + 1, cin_g = c_in / groups, cout_g = c_out / groups;
     const long long red = (long long)n_items * t_out, ck = (long long)cin_g * kernel;
     // the whole layer's c_in * kernel bounds a group's ck; c_in * t is the x offset of the last group's last channel
@@ -287,11 +232,8 @@ static int wgrad_plan(const std::string& f, int n_items, int c_in, int t, int c_
         (long long)c_in * t >= (1LL << 31) || red >= (1LL << 31) - WG_KT || (long long)c_out * (ck + 1) >= (1LL << 31) ||
         (c_out + 31) / 32 > 65535)
         return fail(ADK_ERR_ARG, f + ": layer too large");
-    const int bm = cout_g >= 128 ? 128 : cout_g >= 64 ? 64 : 32;
-    const long long tiles = (long long)groups * ((cout_g + bm - 1) / bm) * ((ck + 1 + 127) / 128);
-    const long long n_steps = (red + WG_KT - 1) / WG_KT;
     long long steps_per = 1, slices = 1;
-    wgrad_slices(tiles, n_steps, steps_per, slices);
+    wgrad_slices(wgrad_tiles(groups, cout_g, ck + 1), (red + WG_KT - 1) / WG_KT, steps_per, slices);
     if (groups * slices > 65535) return fail(ADK_ERR_ARG, f + ": layer too large (groups * slices is the grid's z)");
     g.n_items = n_items; g.c_in = c_in; g.c_out = c_out; g.t = t; g.t_out = t_out; g.ksz = kernel; g.dil = dil; g.stride = stride;
     g.act = act; g.alpha = alpha; g.cin_g = cin_g; g.cout_g = cout_g; g.ck = (int)ck; g.nc_live = (int)ck + 1; g.red = (int)red;
@@ -324,11 +266,7 @@ static int conv_wgrad(const std::string& f, int max_act, const float* dy, const 
     c.nc_live = db ? c.ck + 1 : c.ck;                          // without db its column is not computed
     hipStream_t s = static_cast<hipStream_t>(stream);
     DeviceGuard guard(device_of(dw));
-    const unsigned nx = (unsigned)((c.nc_live + 127) / 128), nz = (unsigned)(groups * c.slices);
-    const int m = c.cout_g;
-    if (m >= 128) hipLaunchKernelGGL((wgrad_kernel<2, 2, 2, 2>), dim3(nx, (m + 127) / 128, nz), dim3(CG_THREADS), 0, s, c);
-    else if (m >= 64) hipLaunchKernelGGL((wgrad_kernel<2, 2, 1, 2>), dim3(nx, (m + 63) / 64, nz), dim3(CG_THREADS), 0, s, c);
-    else hipLaunchKernelGGL((wgrad_kernel<1, 4, 1, 1>), dim3(nx, (m + 31) / 32, nz), dim3(CG_THREADS), 0, s, c);
+    WGRAD_LAUNCH(wgrad_kernel, c, c.cout_g, (unsigned)((c.nc_live + 127) / 128), (unsigned)(groups * c.slices), s);
     ADK_HIP_CHECK(hipGetLastError());
     launch_wgrad_fold(c.ws, dw, db, (int)c_out, c.ck, c.slices, s);
     ADK_HIP_CHECK(hipGetLastError());
